@@ -24,6 +24,15 @@ Also printed in the JSON line: per-kernel HIP-event timings on the launch stream
 HBM roofline, a CPU baseline (the C oracle, a restatement of the reference algorithm, on a
 bounded sample of the same blocks, rank 0 at N=1) and, with --pcie, the host-buffer
 (PCIe-inclusive) rate of every rank, each rank's pinned staging on its GPU's NUMA node.
+
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline figure needs: set
+up, warm up, time the K steps (the per-kernel events are recorded inside them) and print
+the line.  Everything that takes runs of its own -- the full-size verification, the CPU
+baseline, the `strong_stream` sub-line and the --pcie leg -- runs only with --full.
+`--dump-outputs DIR` writes a fixed, seeded sample of what the last timed step left in the
+codeword buffer (the coding shards encode wrote, the data shards reconstruct wrote) as
+DIR/<name>.npy, float32; the inputs are seeded, so two builds can be compared output for
+output.
 """
 
 from __future__ import annotations
@@ -83,8 +92,24 @@ def parse():
     ap.add_argument("--dry-verify-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--dry-stream-verify-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--dry-bdfs", default="", help=argparse.SUPPRESS)  # per-rank PCI addresses (--dry-device)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure: the "
+                         "full-size verification, the CPU baseline, the strong_stream sub-line and, "
+                         "with --pcie, the host-buffer leg (each still has its own off switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write a fixed, seeded sample of the last step's outputs "
+                         "(coding shards from encode, data shards from reconstruct) as DIR/<name>.npy "
+                         "(float32, under 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.strong_stream_default = args.strong_stream < 0
+    if not args.full:
+        # a plain run: the headline measurement only
+        if args.pcie or args.strong_stream > 0:
+            ap.error("--pcie and --strong-stream are measurements of their own: add --full")
+        args.no_verify = args.no_cpu_baseline = True
+        args.strong_stream = 0
     if args.strong_stream < 0:
         args.strong_stream = STREAM_BLOCKS if _headline_shape(args) and not args.stream_blocks else 0
     return args
@@ -393,6 +418,9 @@ def main():
     walls = gather_over_ranks(wall, dist, dev)
     ms_per_step = wall_max * 1e3 / args.steps
 
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, cw.view(n, k + m, S), k, do_enc, do_dec, rank, world, torch)
+
     # full-size property check: zero the erased shards, reconstruct, compare with a fresh
     # regeneration of the data; and a 2-block bit-exact spot check of the parity vs oracle
     verify, ok = None, None
@@ -437,6 +465,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "settle_steps": settle,
+            "full": bool(args.full),
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": plan.scaling,
@@ -596,6 +625,53 @@ def _settle(step, stream, torch, max_steps=200, min_steps=3, tol=0.01, window=4)
             if (max(last) - min(last)) <= tol * min(last):
                 return i + 1
     return max_steps
+
+
+DUMP_ELEMS = 6 << 20  # float32 elements per dumped array: 24 MiB each, two arrays at most
+DUMP_SEED = 0x5EED
+
+
+def _dump_indices(n, rows, S):
+    """The sample --dump-outputs takes of an n x rows x S byte array: (block indices or None
+    for every block, byte columns), sorted, seeded, a function of the shape alone.  The same
+    columns of every shard of every block, as many as DUMP_ELEMS allows; when one column of
+    every shard is already too much, a subset of the blocks as well."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    cols = max(1, min(S, DUMP_ELEMS // max(n * rows, 1)))
+    col_idx = np.sort(rng.choice(S, size=cols, replace=False))
+    blocks = min(n, max(1, DUMP_ELEMS // (rows * cols)))
+    blk_idx = np.sort(rng.choice(n, size=blocks, replace=False)) if blocks < n else None
+    return blk_idx, col_idx
+
+
+def _dump_sample(view, lo, hi, torch):
+    """The _dump_indices sample of view[:, lo:hi] (blocks x shards x shard bytes) as float32."""
+    import numpy as np
+
+    blk_idx, col_idx = _dump_indices(view.shape[0], hi - lo, view.shape[2])
+    part = view[:, lo:hi]
+    if blk_idx is not None:
+        part = part[torch.from_numpy(blk_idx).to(view.device)]
+    out = part[:, :, torch.from_numpy(col_idx).to(view.device)]
+    return out.cpu().numpy().astype(np.float32)
+
+
+def _dump_outputs(path, view, k, do_enc, do_dec, rank, world, torch):
+    """--dump-outputs: what the last timed step computed, as the caller holds it afterwards:
+    `coding` = the m coding shards encode wrote, `data` = the k data shards after reconstruct
+    rewrote the erased ones in place.  Each rank writes its own blocks (file names carry
+    the rank when there is more than one)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    suffix = f"_rank{rank}" if world > 1 else ""
+    if do_enc:
+        np.save(os.path.join(path, f"coding{suffix}.npy"), _dump_sample(view, k, view.shape[1], torch))
+    if do_dec:
+        np.save(os.path.join(path, f"data{suffix}.npy"), _dump_sample(view, 0, k, torch))
 
 
 def _pmc_traffic(kernel, k, m, S, n):

@@ -141,12 +141,66 @@ import sys  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*argv, env_extra=None):
+def _bench(*argv, env_extra=None, full=True):
+    """bench.py as a child process; with --full (the verification, strong_stream and --pcie
+    legs these tests are about run only there) unless `full` is False (a plain run)."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(env_extra or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, cwd=ROOT,
-                          capture_output=True, text=True, timeout=300)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *(["--full"] if full else []), *argv],
+                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+
+
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the line carries the headline fields only: no verification, no
+    strong_stream sub-line; the legs that are runs of their own are refused, not ignored;
+    --steps sets the timed steps; --dump-outputs has nothing to write without a device."""
+    r = _bench("--gpus", "2", "--dry-device", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(tmp_path / "out"), full=False)
+    assert r.returncode == 0, r.stderr
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["verify"] is None and "strong_stream" not in line and "pcie_inclusive" not in line
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] >= 0
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True
+    for extra in (("--pcie",), ("--strong-stream", "1000")):
+        r = _bench("--gpus", "1", "--dry-device", "--steps", "1", *extra, full=False)
+        assert r.returncode == 2 and "--full" in r.stderr, (r.returncode, r.stderr)
+    r = _bench("--gpus", "1", "--dry-device", "--steps", "0", full=False)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_bench_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs' sample: float32, the same seeded byte columns of every shard of every
+    block from call to call, within the per-array budget, values equal to the bytes picked."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(7)
+    view = torch.randint(0, 256, (5, 12, 96), dtype=torch.uint8, generator=g)
+    a = bench._dump_sample(view, 4, 12, torch)
+    b = bench._dump_sample(view.clone(), 4, 12, torch)
+    assert a.dtype == np.float32 and a.shape == (5, 8, 96) and np.array_equal(a, b)
+    assert np.array_equal(a, view[:, 4:12].numpy().astype(np.float32))  # small: everything fits
+    old = bench.DUMP_ELEMS
+    try:
+        bench.DUMP_ELEMS = 5 * 8 * 10  # 10 columns per shard
+        c = bench._dump_sample(view, 4, 12, torch)
+        assert c.shape == (5, 8, 10) and c.size <= bench.DUMP_ELEMS
+        cols = [j for j in range(96) if np.array_equal(view[:, 4:12, j].numpy(), c[:, :, 0])]
+        assert cols, "first sampled column is a column of the view"
+        assert np.array_equal(c, bench._dump_sample(view, 4, 12, torch))
+        bench.DUMP_ELEMS = 3 * 8  # one column, and not every block
+        d = bench._dump_sample(view, 4, 12, torch)
+        assert d.shape == (3, 8, 1)
+    finally:
+        bench.DUMP_ELEMS = old
 
 
 @pytest.mark.parametrize("extra,firsts", [((), [0, 4096]), (("--stream-blocks", "65536"), [0, 32768])])

@@ -11,7 +11,7 @@ for r in $(seq 1 $rounds); do
   for pt in "$@"; do
     label=${pt%%:*}; args=${pt#*:}; args=${args//,/ }
     for lib in $libs; do
-      AG_RS_LIB_NAME=$lib timeout -k 10 200 python3 bench.py --steps 10 --warmup 10 --no-cpu-baseline $args \
+      AG_RS_LIB_NAME=$lib timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 10 --no-cpu-baseline $args \
         > gpurun_out/ab_pt.json 2> gpurun_out/ab_pt.err
       rc=$?; [ $rc = 0 ] || { tail -3 gpurun_out/ab_pt.err; echo "STOP $lib $label exit $rc"; exit $rc; }
       python3 - "$lib" "$label" "$r" <<'PY'

@@ -7,8 +7,8 @@
 # ends the session -- no retries, nothing further on the GPU):
 #   tests [PYTEST ARGS]      pytest -m gpu (log: gpurun_out/pytest_gpu.log)
 #   smoke                    __graft_entry__.smoke()
-#   bench [BENCH ARGS]       bench.py (default: the driver's --steps 20 --warmup 5) -> bench.json
-#   point LABEL [ARGS]       one bench.py line (10 timed steps, no CPU baseline) -> points.jsonl
+#   bench [BENCH ARGS]       bench.py (default: --full --steps 20 --warmup 5, every leg) -> bench.json
+#   point LABEL [ARGS]       one bench.py --full line (10 timed steps, verified, no CPU baseline) -> points.jsonl
 #   points PRESET            a preset list of points: tail | lost | w128 | random | c4 | c4x64
 #   coder [ARGS]             bench_coder.py over its four arrival shapes -> coder.jsonl
 #   coder_short [ARGS]       bench_coder.py --random-patterns at four non-maximal payload lengths
@@ -46,7 +46,7 @@ EOF
 
 point() {
   local label=$1; shift
-  timeout -k 10 300 $PY bench.py --steps 10 --warmup 5 --no-cpu-baseline "$@" > $OUT/pt.json 2> $OUT/pt.err
+  timeout -k 10 300 $PY bench.py --full --steps 10 --warmup 5 --no-cpu-baseline "$@" > $OUT/pt.json 2> $OUT/pt.err
   local rc=$?
   [ $rc = 0 ] || { tail -5 $OUT/pt.err; fail "point $label" $rc; }
   jsonl_last $OUT/pt.json "$label" $OUT/points.jsonl
@@ -74,7 +74,7 @@ points() {
         for bb in 65536 262144 1048576 4194304; do
           IFS=: read -r k m <<< "$km"
           nb=$(( (4 << 30) / bb ))
-          timeout -k 10 300 $PY bench.py --k $k --m $m --block-bytes $bb --nblocks $nb --steps 10 --warmup 30 \
+          timeout -k 10 300 $PY bench.py --full --k $k --m $m --block-bytes $bb --nblocks $nb --steps 10 --warmup 30 \
             --no-cpu-baseline > $OUT/pt.json 2> $OUT/pt.err
           rc=$?; [ $rc = 0 ] || { tail -5 $OUT/pt.err; fail "c4 $km $bb" $rc; }
           jsonl_last $OUT/pt.json "c4_${k}x${m}_${bb}" $OUT/points.jsonl
@@ -100,7 +100,7 @@ step() {
       timeout -k 10 300 $PY -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       local rc=$?; echo "smoke exit $rc"; tail -2 $OUT/smoke.log; [ $rc = 0 ] || fail smoke $rc ;;
     bench)
-      [ $# -gt 0 ] || set -- --steps 20 --warmup 5
+      [ $# -gt 0 ] || set -- --full --steps 20 --warmup 5
       timeout -k 10 600 $PY bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
       local rc=$?; echo "bench exit $rc"; cat $OUT/bench.json; tail -3 $OUT/bench.err; [ $rc = 0 ] || fail bench $rc ;;
     point) point "$@" ;;
