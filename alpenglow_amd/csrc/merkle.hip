@@ -17,7 +17,11 @@
 //                         lane: v_alignbit rotations, v_bitop3 sigma XORs / ch / maj, v_add3)
 //   merkle_level_kernel   one launch per tree level, one thread per (slice, pair)
 //   merkle_proof_kernel   one thread per leaf: its create_proof siblings
-//   merkle_verify_kernel  one thread per (leaf, index, root, proof): derive_root == root.
+//   merkle_verify_kernel  one thread per (leaf, index, root, proof): derive_root == root;
+//                         optionally a proof length and the check_proof_last rule per item
+//   block_tree_kernel     one workgroup per block: the double-Merkle tree over its slice roots
+//                         (DoubleMerkleTree, merkle.rs:263), all levels in LDS, one launch
+//   block_proof_kernel    every slice's create_proof of a block tree, from its nodes
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -198,7 +202,8 @@ __global__ __launch_bounds__(256) void merkle_proof_kernel(const MerkleBuildPara
 // check_proof (merkle.rs:374-387, 417-428) for one leaf per thread; derive_root (:411-428)
 // when roots_out is set.
 // LIST: thread i verifies leaf list[i] for i < list[n] (the compacted active leaves).
-template <bool A4, bool LIST>
+// ITEM: per-item proof length and the check_proof_last rule (proof_len / last; check mode only).
+template <bool A4, bool LIST, bool ITEM = false>
 __global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyParams p) {
   uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if constexpr (LIST) {
@@ -213,9 +218,28 @@ __global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyPa
     store_digest(p.leaf_nodes + (t / p.leaves_per_tree) * p.leaf_nodes_stride + 32 * (t % p.leaves_per_tree), node);
   uint32_t idx = p.index[t];
   const uint8_t* pr = p.proofs + t * p.proofs_stride;
-  for (uint32_t h = 0; h < p.height; ++h) {
+  uint32_t height = p.height;
+  bool last = false, canonical = true;
+  if constexpr (ITEM) {
+    height = p.proof_len[t];
+    // merkle.rs:381-383 / :398-400 (a proof longer than EMPTY_ROOTS), and a proof the item's
+    // stride cannot hold: rejected before any of it is read
+    if (height > static_cast<uint32_t>(kMerkleMaxHeight) || 32ull * height > p.proofs_stride) {
+      p.ok[t] = 0;
+      return;
+    }
+    last = p.last && p.last[t];
+  }
+  for (uint32_t h = 0; h < height; ++h) {
     uint32_t s[8], nn[8];
     load_digest(pr + 32 * h, s);
+    if constexpr (ITEM) {
+      // derive_hash_root_last (merkle.rs:436-452): a right-hand sibling must be EMPTY_ROOTS[h]
+      if (last && !(idx & 1)) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) canonical = canonical && s[i] == p.empty_roots[8 * h + i];
+      }
+    }
     if (idx & 1) hash_pair(s, node, nn); else hash_pair(node, s, nn);
 #pragma unroll
     for (int i = 0; i < 8; ++i) node[i] = nn[i];
@@ -229,7 +253,7 @@ __global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyPa
   }
   uint32_t root[8];
   load_digest(p.roots + t * p.roots_stride, root);
-  bool ok = true;
+  bool ok = canonical;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ok = ok && node[i] == root[i];
   p.ok[t] = ok ? 1 : 0;
@@ -260,7 +284,146 @@ __global__ __launch_bounds__(1024) void compact_active_kernel(const uint8_t* __r
   if (a) list[base + wcnt[wave] + __builtin_popcountll(m & ((uint64_t{1} << lane) - 1))] = static_cast<uint32_t>(t);
 }
 
+// ---- block trees: the double-Merkle tree over a block's slice roots -----------------------
+//
+// One workgroup per block, the whole tree in one launch: a block hash is wanted the moment the
+// block's last slice lands, usually for one block, and the tree is a chain of up to 10
+// dependent levels over at most 1024 leaves of 2 compressions each -- per-level launches (the
+// slice trees' shape above) would put 10 kernel boundaries into a chain of ~5 100 compressions
+// (not built, so not measured).  The
+// current level lives in LDS as native state words, ping-ponged between a 1024- and a
+// 512-digest buffer (48 KiB); bytes are swapped only at the global loads and stores.  Each
+// level: hash pairs from one buffer into the other, barrier.  (The fused one-wave-per-slice
+// build that lost for the slice trees had 17-block leaves and 65 536 trees; here the leaves
+// are short and the trees few.)
+// Measured on an MI355X (profiles/block_tree_bench.jsonl, kernel trace): one 1024-slice block
+// 102 us, 64 such blocks 113 us -- the time is the chain, not the work: a level is one
+// hash_pair, ~3 600 VALU that a lone wave issues at ~4 cycles each, 8-9 us, times 10 levels,
+// plus the leaves.  Workgroup size, kernel time for 1 / 64 blocks: 256 threads 105 / 115 us,
+// 512 threads 102 / 113 us, 1024 threads 110 / 122 us (128 VGPRs: 11 spilled); 512 it is.
+__device__ __forceinline__ void lds_put(uint4* lv, uint32_t j, const uint32_t h[8]) {
+  lv[2 * j] = make_uint4(h[0], h[1], h[2], h[3]);
+  lv[2 * j + 1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+__device__ __forceinline__ void lds_get(const uint4* lv, uint32_t j, uint32_t h[8]) {
+  const uint4 a = lv[2 * j], b = lv[2 * j + 1];
+  h[0] = a.x;
+  h[1] = a.y;
+  h[2] = a.z;
+  h[3] = a.w;
+  h[4] = b.x;
+  h[5] = b.y;
+  h[6] = b.z;
+  h[7] = b.w;
+}
+
+constexpr uint32_t kBlockTreeThreads = 512;
+__global__ __launch_bounds__(kBlockTreeThreads) void block_tree_kernel(const BlockTreeParams p) {
+  __shared__ uint4 lv_a[2 * kBlockMaxSlices];  // levels 0, 2, 4, ..: at most 1024 digests
+  __shared__ uint4 lv_b[kBlockMaxSlices];      // levels 1, 3, 5, ..: at most 512 digests
+  const uint64_t b = blockIdx.x;
+  const uint32_t n = p.count[b];
+  if (n > kBlockMaxSlices) return;  // the launcher's caller validates the counts; never past the LDS
+  const uint8_t* in = p.slice_roots + 32 * p.first[b];
+  uint8_t* nd = p.nodes ? p.nodes + b * p.nodes_stride : nullptr;
+  uint8_t* out = p.block_hashes + 32 * b;
+  // leaves: SHA-256(LEAF_LABEL || root) = one data block and the constant padding block
+  for (uint32_t j = threadIdx.x; j < n; j += kBlockTreeThreads) {
+    uint32_t st[8], w[16];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      st[i] = sha::kIv[i];
+      w[i] = sha::kLeafLabel.w[i];
+    }
+    load_digest(in + 32 * static_cast<uint64_t>(j), w + 8);
+    sha::compress(st, w);
+    w[0] = 0x80000000u;
+#pragma unroll
+    for (int i = 1; i < 15; ++i) w[i] = 0;
+    w[15] = 64 * 8;
+    sha::compress(st, w);
+    lds_put(lv_a, j, st);
+    if (nd) store_digest(nd + 32 * j, st);
+    if (n == 1) store_digest(out, st);  // a one-slice block: height 0, the hash is the leaf
+  }
+  __syncthreads();
+  uint4* src = lv_a;
+  uint4* dst = lv_b;
+  uint32_t off = 0, len = n;  // n is uniform in the workgroup: so is every barrier below
+  for (uint32_t h = 0; len > 1; ++h) {
+    const uint32_t nlen = (len + 1) / 2;
+    for (uint32_t j = threadIdx.x; j < nlen; j += kBlockTreeThreads) {
+      uint32_t l[8], r[8], o[8];
+      lds_get(src, 2 * j, l);
+      if (2 * j + 1 < len) {
+        lds_get(src, 2 * j + 1, r);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) r[i] = p.empty_roots[8 * h + i];
+      }
+      hash_pair(l, r, o);
+      lds_put(dst, j, o);
+      if (nd) store_digest(nd + 32 * (off + len + j), o);
+      if (nlen == 1) store_digest(out, o);
+    }
+    __syncthreads();
+    uint4* t = src;
+    src = dst;
+    dst = t;
+    off += len;
+    len = nlen;
+  }
+}
+
+// create_proof for every slice of a block from its nodes: blockIdx.x = the block, blockIdx.y
+// splits its 16-byte pieces (one block's 1024 x 10 digests are 20 480 of them).  Lane-consecutive
+// pieces as in merkle_proof_kernel; the height is the block's own.
+constexpr unsigned kBlockProofSplit = 8;
+__global__ __launch_bounds__(256) void block_proof_kernel(const BlockTreeParams p) {
+  const uint64_t b = blockIdx.x;
+  const uint32_t n = p.count[b];
+  if (n > kBlockMaxSlices) return;
+  uint32_t height = 0;
+  for (uint32_t l = n; l > 1; l = (l + 1) / 2) ++height;
+  const uint8_t* nd = p.nodes + b * p.nodes_stride;
+  uint8_t* dst = p.proofs + b * p.proofs_stride;
+  const uint32_t pieces = n * height * 2;
+  for (uint32_t i = blockIdx.y * 256 + threadIdx.x; i < pieces; i += kBlockProofSplit * 256) {
+    const uint32_t j = i / (2 * height), r = i - j * 2 * height, h = r >> 1, half = r & 1;
+    uint32_t off = 0, l = n;
+    for (uint32_t g = 0; g < h; ++g) {
+      off += l;
+      l = (l + 1) / 2;
+    }
+    const uint32_t sib = (j >> h) ^ 1;
+    uint4 v;
+    if (sib >= l) {
+      const uint32_t* e = p.empty_roots + 8 * h + 4 * half;
+      v = make_uint4(sha::bswap(e[0]), sha::bswap(e[1]), sha::bswap(e[2]), sha::bswap(e[3]));
+    } else {
+      v = *reinterpret_cast<const uint4*>(nd + 32 * (off + sib) + 16 * half);
+    }
+    *reinterpret_cast<uint4*>(dst + 16 * static_cast<uint64_t>(i)) = v;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_block_tree(const BlockTreeParams& p, hipStream_t stream) {
+  if (p.nblocks == 0) return hipSuccess;
+  if (p.nblocks > 0x7FFFFFFFull || !p.first || !p.count || !p.slice_roots || !p.empty_roots || !p.block_hashes ||
+      (p.proofs && !p.nodes) ||
+      (reinterpret_cast<uintptr_t>(p.slice_roots) | reinterpret_cast<uintptr_t>(p.block_hashes) |
+       reinterpret_cast<uintptr_t>(p.nodes) | reinterpret_cast<uintptr_t>(p.proofs) | p.nodes_stride |
+       p.proofs_stride) % 16)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(block_tree_kernel, dim3(static_cast<unsigned>(p.nblocks)), dim3(kBlockTreeThreads), 0, stream,
+                     p);
+  if (p.proofs)
+    hipLaunchKernelGGL(block_proof_kernel, dim3(static_cast<unsigned>(p.nblocks), kBlockProofSplit), dim3(256), 0,
+                       stream, p);
+  return hipGetLastError();
+}
 
 hipError_t launch_merkle_build(const MerkleBuildParams& p, uint8_t* nodes, uint64_t nodes_stride,
                                hipStream_t stream) {
@@ -303,6 +466,13 @@ hipError_t launch_merkle_verify(const MerkleVerifyParams& p, hipStream_t stream)
   if (groups > 0x7FFFFFFFull) return hipErrorInvalidValue;
   const bool a16 = (reinterpret_cast<uintptr_t>(p.leaves) | p.leaf_stride | p.group_stride) % 16 == 0;
   const dim3 grid(static_cast<unsigned>(groups));
+  if (p.proof_len) {  // per-item lengths: plain check mode only
+    if (p.roots_out || p.active || !p.empty_roots) return hipErrorInvalidValue;
+    if (a16) hipLaunchKernelGGL((merkle_verify_kernel<true, false, true>), grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((merkle_verify_kernel<false, false, true>), grid, dim3(256), 0, stream, p);
+    return hipGetLastError();
+  }
+  if (p.last) return hipErrorInvalidValue;
   if (p.active && p.list && p.n < 0xFFFFFFFFull) {
     if (hipMemsetAsync(p.list + p.n, 0, 4, stream) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_active_kernel, dim3(static_cast<unsigned>((p.n + 1023) / 1024)), dim3(1024), 0, stream,

@@ -72,8 +72,37 @@ struct MerkleVerifyParams {
   uint32_t leaves_per_tree;    // level 0, launch_merkle_build's nodes layout)
   uint64_t group_stride;       // leaf t at leaves + grouped_row_offset(t, leaf_stride, group_stride,
   uint32_t skip_row;           // skip_row) (group_stride 0: t * leaf_stride)
+  // nullable pair (check mode only; needs empty_roots): item t's proof is proof_len[t] digests
+  // instead of `height` (> 32, or more than proofs_stride holds: ok = 0, its proof is not read),
+  // and with last[t] != 0 the check is check_proof_last (merkle.rs:394-407, 436-452): every
+  // sibling on the right must be EMPTY_ROOTS[its height].  last null = all 0.
+  const uint32_t* proof_len;
+  const uint8_t* last;
+  const uint32_t* empty_roots;  // device [32][8] big-endian words
 };
 hipError_t launch_merkle_verify(const MerkleVerifyParams& p, hipStream_t stream);
+
+// MAX_SLICES_PER_BLOCK (slice_index.rs:15): a block's double-Merkle tree has at most 1024 leaves.
+constexpr uint32_t kBlockMaxSlices = 1024;
+
+// DoubleMerkleTree::new (merkle.rs:263, 281-333) for nblocks blocks: block b's leaves are the
+// count[b] slice roots (32 B each, 1 <= count[b] <= 1024) from slice_roots + 32 * first[b].
+// Outputs (device): block_hashes[b] (32 B, the BlockHash); nodes (optional) = the reference's
+// `nodes` vector per block at nodes_stride; proofs (optional, needs nodes) = create_proof(j) for
+// every slice j, height(count[b]) digests each, at proofs + b * proofs_stride.
+struct BlockTreeParams {
+  const uint64_t* first;  // device [nblocks]
+  const uint32_t* count;  // device [nblocks]
+  uint64_t nblocks;
+  const uint8_t* slice_roots;
+  const uint32_t* empty_roots;  // device [32][8] big-endian words (EMPTY_ROOTS)
+  uint8_t* block_hashes;
+  uint8_t* nodes;  // may be null (unless proofs is set)
+  uint64_t nodes_stride;
+  uint8_t* proofs;  // may be null
+  uint64_t proofs_stride;
+};
+hipError_t launch_block_tree(const BlockTreeParams& p, hipStream_t stream);
 
 // EMPTY_ROOTS[h] as big-endian words (host; the same SHA-256 code as the kernels).
 void merkle_empty_roots(uint32_t out[kMerkleMaxHeight][8]);

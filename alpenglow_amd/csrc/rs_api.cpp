@@ -168,6 +168,9 @@ struct ag_rs_ctx {
   DevBuf d_corr, d_corrk, d_corrblocks;     // correction decoder: patterns, K picks, block ids
   DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
   DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
+  DevBuf d_block_meta;                      // block trees: first[nblocks] (u64), then count[nblocks] (u32)
+  PinBuf h_block_meta;                      // its pinned host staging
+  hipEvent_t block_meta_ev = nullptr;       // recorded after its upload
   DevBuf d_aon_lens, d_aon_digests, d_aon_keys;  // all-or-nothing transforms
   DevBuf d_aon_lens2;                            // the side stream's SHA-256 lengths (AONT deshred)
   hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
@@ -327,7 +330,7 @@ struct ag_rs_ctx {
     }
     for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &d_mask,
                       &d_xmask, &d_rows, &d_xblocks, &d_x128, &d_rows128, &d_syn, &d_synblocks, &d_corr, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_in, &stage_out, &stage_pad, &stage_mask, &d_slice_meta, &one_in,
-                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present})
+                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta})
       b->release();
     for (DevBuf& b : pipe) b.release();
     if (present_ev) {
@@ -340,6 +343,11 @@ struct ag_rs_ctx {
       (void)hipEventDestroy(lens_ev);
     }
     h_lens.release();
+    if (block_meta_ev) {
+      (void)hipEventSynchronize(block_meta_ev);
+      (void)hipEventDestroy(block_meta_ev);
+    }
+    h_block_meta.release();
     h_strip.release();
     h_slice_meta.release();
     h_pipe_meta.release();
@@ -1664,6 +1672,92 @@ int ag_merkle_verify_batch(ag_rs_ctx* c, size_t n, size_t leaf_bytes, const uint
   p.proofs_stride = proofs_stride;
   p.n = n;
   p.ok = ok;
+  return ag::launch_merkle_verify(p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+}
+
+// ---- block trees: the double-Merkle tree over a block's slice roots -----------------------
+
+int ag_block_tree_batch(ag_rs_ctx* c, size_t nblocks, const uint32_t* count, const uint8_t* slice_roots,
+                        uint8_t* block_hashes, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
+                        size_t proofs_stride) {
+  static_assert(AG_BLOCK_MAX_SLICES == ag::kBlockMaxSlices);
+  if (!c) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nblocks == 0) return AG_RS_OK;
+  if (!count || !slice_roots || !block_hashes || nblocks > 0x7FFFFFFFull) return AG_RS_ERR_INVALID_ARGUMENT;
+  uint32_t mx = 0;
+  for (size_t b = 0; b < nblocks; ++b) {
+    if (count[b] == 0 || count[b] > AG_BLOCK_MAX_SLICES) return AG_RS_ERR_INVALID_ARGUMENT;
+    mx = std::max(mx, count[b]);
+  }
+  // node count and height * count both grow with the count: the largest block sets the strides
+  if ((reinterpret_cast<uintptr_t>(slice_roots) | reinterpret_cast<uintptr_t>(block_hashes) |
+       reinterpret_cast<uintptr_t>(nodes) | reinterpret_cast<uintptr_t>(proofs)) % 16 ||
+      (nodes && (nodes_stride % 16 || (nblocks > 1 && nodes_stride < 32 * ag_merkle_node_count(mx)))) ||
+      (proofs && (proofs_stride % 16 || (nblocks > 1 && proofs_stride < 32 * ag_merkle_height(mx) * mx))))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  int st = c->enter();
+  if (st || (st = ensure_empty_roots(c))) return st;
+  // offsets and counts go up through pinned staging on the context stream, as the coder's
+  // payload lengths do: the staging is rewritten once its last upload has completed
+  if (c->block_meta_ev) AG_HIP(hipEventSynchronize(c->block_meta_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->block_meta_ev, hipEventDisableTiming));
+  if ((st = c->h_block_meta.ensure(12 * nblocks)) || (st = c->d_block_meta.ensure(12 * nblocks, c->stream))) return st;
+  uint64_t* first = c->h_block_meta.as<uint64_t>();
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(first + nblocks);
+  uint64_t at = 0;
+  for (size_t b = 0; b < nblocks; ++b) {
+    first[b] = at;
+    cnt[b] = count[b];
+    at += count[b];
+  }
+  AG_HIP(hipMemcpyAsync(c->d_block_meta.ptr, c->h_block_meta.ptr, 12 * nblocks, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->block_meta_ev, c->stream));
+  ag::BlockTreeParams p{};
+  p.first = c->d_block_meta.as<uint64_t>();
+  p.count = reinterpret_cast<const uint32_t*>(p.first + nblocks);
+  p.nblocks = nblocks;
+  p.slice_roots = slice_roots;
+  p.empty_roots = c->d_empty_roots.as<uint32_t>();
+  p.block_hashes = block_hashes;
+  p.nodes = nodes;
+  p.nodes_stride = nodes_stride;
+  p.proofs = proofs;
+  p.proofs_stride = proofs_stride;
+  if (proofs && !nodes) {  // the proofs are gathered from the nodes: scratch when the caller wants none
+    p.nodes_stride = (32 * ag_merkle_node_count(mx) + 255) / 256 * 256;
+    if ((st = c->d_merkle_nodes.ensure(nblocks * p.nodes_stride, c->stream))) return st;
+    p.nodes = c->d_merkle_nodes.as<uint8_t>();
+  }
+  return ag::launch_block_tree(p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+}
+
+int ag_block_proof_check_batch(ag_rs_ctx* c, size_t n, const uint8_t* slice_roots, size_t roots_stride,
+                               const uint32_t* index, const uint8_t* block_hashes, size_t hashes_stride,
+                               const uint8_t* proofs, size_t proofs_stride, const uint32_t* proof_len,
+                               const uint8_t* last, uint8_t* ok) {
+  if (!c) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return AG_RS_OK;
+  // proofs may be null only with a zero stride, which holds no digest: any proof_len > 0 is then ok = 0
+  if (!slice_roots || !index || !block_hashes || !proof_len || !ok || (!proofs && proofs_stride) ||
+      hashes_stride % 16 || proofs_stride % 16 || reinterpret_cast<uintptr_t>(block_hashes) % 16 ||
+      reinterpret_cast<uintptr_t>(proofs) % 16 || (n > 1 && roots_stride < 32))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  int st = c->enter();
+  if (st || (st = ensure_empty_roots(c))) return st;
+  ag::MerkleVerifyParams p{};
+  p.leaves = slice_roots;
+  p.leaf_stride = roots_stride;
+  p.leaf_bytes = 32;
+  p.index = index;
+  p.roots = block_hashes;
+  p.roots_stride = hashes_stride;
+  p.proofs = proofs;
+  p.proofs_stride = proofs_stride;
+  p.n = n;
+  p.ok = ok;
+  p.proof_len = proof_len;
+  p.last = last;
+  p.empty_roots = c->d_empty_roots.as<uint32_t>();
   return ag::launch_merkle_verify(p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
 

@@ -76,7 +76,7 @@ EXPORTS = (
     "ag_rs_encoder_new_on_device", "ag_rs_decoder_new_on_device", "ag_rs_coder_new_on_device",
     "ag_rs_coder_shred_batch", "ag_rs_coder_deshred_batch",
     "ag_merkle_empty_root", "ag_merkle_height", "ag_merkle_node_count", "ag_merkle_build_batch",
-    "ag_merkle_verify_batch",
+    "ag_merkle_verify_batch", "ag_block_tree_batch", "ag_block_proof_check_batch",
     "ag_aes128_encrypt_block", "ag_cipher_apply_keystream_batch", "ag_sha256_batch", "ag_aon_encrypt_batch",
     "ag_aon_decrypt_batch",
     "ag_ed25519_public_key_batch", "ag_ed25519_sign_batch", "ag_ed25519_verify_batch", "ag_shred_validate_batch",
@@ -152,6 +152,8 @@ def load():
         "ag_merkle_node_count": ([sz], sz),
         "ag_merkle_build_batch": ([p, sz, sz, sz, p, sz, sz, p, p, sz, p, sz], i),
         "ag_merkle_verify_batch": ([p, sz, sz, p, sz, p, p, sz, p, sz, sz, p], i),
+        "ag_block_tree_batch": ([p, sz, p, p, p, p, sz, p, sz], i),
+        "ag_block_proof_check_batch": ([p, sz, p, sz, p, p, sz, p, sz, p, p, p], i),
         "ag_aes128_encrypt_block": ([p, p, p], i),
         "ag_cipher_apply_keystream_batch": ([p, sz, p, p, sz, p], i),
         "ag_sha256_batch": ([p, sz, p, sz, p, p], i),
@@ -686,6 +688,31 @@ def merkle_verify_batch(ctx: Context, n: int, leaf_bytes: int, leaves, leaf_stri
     _check(load().ag_merkle_verify_batch(ctx.handle, n, leaf_bytes, _ptr(leaves), leaf_stride, _ptr(index),
                                          _ptr(roots), roots_stride, _ptr(proofs), proofs_stride, height,
                                          _ptr(ok)), "ag_merkle_verify_batch")
+
+
+# ---- block trees: the double-Merkle tree over a block's slice roots (merkle.rs:263) ----
+
+BLOCK_MAX_SLICES = 1024
+
+
+def block_tree_batch(ctx: Context, nblocks: int, counts, slice_roots, block_hashes, nodes=None,
+                     nodes_stride: int = 0, proofs=None, proofs_stride: int = 0):
+    """DoubleMerkleTree::new + get_root (+ nodes, + create_proof for every slice) for nblocks
+    blocks: counts (host) = slices per block, their roots contiguous in slice_roots (device)."""
+    a = _u32(counts, nblocks)
+    _check(load().ag_block_tree_batch(ctx.handle, nblocks, a.ctypes.data, _optr(slice_roots), _optr(block_hashes),
+                                      _optr(nodes), nodes_stride, _optr(proofs), proofs_stride),
+           "ag_block_tree_batch")
+
+
+def block_proof_check_batch(ctx: Context, n: int, slice_roots, roots_stride: int, index, block_hashes,
+                            hashes_stride: int, proofs, proofs_stride: int, proof_len, last, ok):
+    """check_proof (last[t] = 0 or last None) / check_proof_last (last[t] = 1) for n slice roots
+    against their block hashes, proof_len[t] digests each (device buffers); ok[t] = 1 / 0."""
+    _check(load().ag_block_proof_check_batch(ctx.handle, n, _ptr(slice_roots), roots_stride, _ptr(index),
+                                             _ptr(block_hashes), hashes_stride, _optr(proofs), proofs_stride,
+                                             _ptr(proof_len), _optr(last), _ptr(ok)),
+           "ag_block_proof_check_batch")
 
 
 # ---- all-or-nothing payload transforms (AONT / PETS; shredder.rs:403-528) -------------

@@ -12,6 +12,9 @@ Inputs are device-resident random shreds (splitmix64).  Prints one JSON line: sl
 build+verify, per-kernel HIP-event times, the HBM-read roofline of each kernel (each kernel
 reads the shreds once; the work is SHA-256 on the VALU), and a CPU baseline (the oracle:
 Python hashlib / OpenSSL SHA-256, one thread, bounded sample).
+
+--block-tree times the block trees instead (ag_block_tree_batch: the double-Merkle tree over a
+block's slice roots), one JSON line per shape; see block_tree_leg.
 """
 from __future__ import annotations
 
@@ -26,6 +29,79 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0
 
 
+def block_tree_leg(args):
+    """--block-tree: ag_block_tree_batch (the double-Merkle tree over a block's slice roots) at
+    1 x 1024 and 64 x 1024 slices, hashes only and hashes + every slice's proof.  Per call, HIP
+    events around it on the context stream (the upload of the counts, the tree kernel, the proof
+    kernel) and the host's wall time from the call to the end of a synchronise; median and
+    minimum over --steps calls.  One JSON line per shape; the same trees through
+    oracle/merkle_oracle.py on one host thread ride along as context."""
+    import statistics
+
+    import torch
+
+    from alpenglow_amd import rs
+
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import merkle_oracle as mo
+
+    dev = torch.device("cuda:0")
+    ctx = rs.Context(0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)
+    n, steps = 1024, max(args.steps, 20)
+    h = rs.merkle_height(n)
+    pstride = 32 * h * n
+    for nblocks in (1, 64):
+        counts = [n] * nblocks
+        roots = torch.empty((nblocks * n, 32), dtype=torch.uint8, device=dev)
+        rs.fill_splitmix(ctx, roots, nblocks * n, 32, 32, 0xB10C7EE0)
+        hashes = torch.empty((nblocks, 32), dtype=torch.uint8, device=dev)
+        proofs = torch.empty((nblocks, pstride), dtype=torch.uint8, device=dev)
+        host = roots.cpu().numpy()
+        t0 = time.perf_counter()
+        tree = mo.MerkleTree([host[j].tobytes() for j in range(n)])
+        cpu_tree_us = (time.perf_counter() - t0) * 1e6
+        t0 = time.perf_counter()
+        want_proofs = b"".join(b"".join(tree.create_proof(j)) for j in range(n))
+        cpu_proofs_us = (time.perf_counter() - t0) * 1e6
+        modes = {}
+        for mode, pr in (("hashes", None), ("hashes_and_proofs", proofs)):
+            def call():
+                rs.block_tree_batch(ctx, nblocks, counts, roots, hashes, None, 0, pr, pstride if pr is not None else 0)
+            for _ in range(max(args.warmup, 3)):
+                call()
+            torch.cuda.synchronize()
+            dev_us, wall_us = [], []
+            for _ in range(steps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0 = time.perf_counter()
+                e0.record(stream)
+                call()
+                e1.record(stream)
+                torch.cuda.synchronize()
+                wall_us.append((time.perf_counter() - t0) * 1e6)
+                dev_us.append(e0.elapsed_time(e1) * 1e3)
+            modes[mode] = {"device_us_median": statistics.median(dev_us), "device_us_min": min(dev_us),
+                           "wall_us_median": statistics.median(wall_us), "wall_us_min": min(wall_us)}
+        ok = hashes[0].cpu().numpy().tobytes() == tree.root() and \
+            proofs[0].cpu().numpy().tobytes() == want_proofs
+        us = modes["hashes"]["device_us_median"]
+        print(json.dumps({
+            "metric": "us per ag_block_tree_batch call (double-Merkle tree over slice roots, SHA-256)",
+            "value": us, "unit": "us", "higher_is_better": False, "n_gpus": 1, "steps": steps,
+            "config": {"blocks": nblocks, "slices_per_block": n},
+            "blocks_per_s": nblocks / (us * 1e-6),
+            "sha256_blocks": nblocks * (2 * n + 3 * (rs.merkle_node_count(n) - n)),
+            "modes": modes,
+            "verify": {"block_0_hash_and_proofs_match_oracle": ok},
+            "cpu_context": {"tree_us_per_block": cpu_tree_us, "proofs_us_per_block": cpu_proofs_us, "cores": 1,
+                            "kind": "oracle/merkle_oracle.py (hashlib SHA-256), one block, one thread"},
+        }), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--slices", type=int, default=65536)
@@ -34,7 +110,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--block-tree", action="store_true",
+                    help="time ag_block_tree_batch (block hashes over slice roots) instead of the slice trees")
     args = ap.parse_args()
+    if args.block_tree:
+        return block_tree_leg(args)
     import torch
 
     from alpenglow_amd import rs

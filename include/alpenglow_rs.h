@@ -17,7 +17,8 @@
  *      (the GPU-shaped entry points: many blocks per launch)
  *   4. context / stream / utility
  *   5. ag_merkle_*     -- the slice Merkle tree over the shreds (crypto/merkle.rs,
- *      shredder.rs:628-632), batched on the device
+ *      shredder.rs:628-632), batched on the device; ag_block_* -- the double-Merkle tree
+ *      over a block's slice roots (the BlockHash) and the repair responses' proof checks
  *   6. ag_aon_* / ag_cipher_* / ag_sha256_* -- the AONT / PETS shredders' payload
  *      transforms (shredder.rs:403-528, crypto/cipher.rs, crypto/hash.rs)
  *   7. ag_ed25519_* / ag_shred_validate_batch / ag_slice_sign_batch -- the leader's slice
@@ -308,6 +309,40 @@ int ag_merkle_verify_batch(ag_rs_ctx* ctx, size_t n, size_t leaf_bytes, const ui
                            size_t leaf_stride, const uint32_t* index, const uint8_t* roots,
                            size_t roots_stride, const uint8_t* proofs, size_t proofs_stride, size_t height,
                            uint8_t* ok);
+
+/* ---- 5b. block trees: the double-Merkle tree over a block's slice roots ----------------
+ * DoubleMerkleTree (merkle.rs:263): the same MerkleTree with the block's slice roots as leaves,
+ *   leaf = SHA-256(LEAF_LABEL || slice root); its root is the BlockHash -- what
+ * BlockData::try_reconstruct_block computes when a block completes (slot_block_data.rs:390-394),
+ * the block id the next block's first slice carries as its parent.  At most
+ * MAX_SLICES_PER_BLOCK (slice_index.rs:15) slices per block.  Asynchronous on the context
+ * stream; every buffer is device memory except `count`. */
+#define AG_BLOCK_MAX_SLICES 1024
+
+/* DoubleMerkleTree::new + get_root (+ nodes, + create_proof for every slice) for nblocks blocks
+ * in one launch.  count (HOST, consumed before the call returns): block b has count[b] slices,
+ * 1 <= count[b] <= 1024; its slice roots are the 32-byte digests from slice_roots +
+ * 32 * (count[0] + .. + count[b-1]) -- the layout of every `roots` output of this library.
+ * block_hashes: 32 B per block.  nodes (nullable): ag_merkle_node_count(count[b]) digests per
+ * block at nodes_stride, reference order.  proofs (nullable): slice j's proof is
+ * h_b = ag_merkle_height(count[b]) digests at proofs + b*proofs_stride + 32*h_b*j.
+ * Pointers and strides must be 16-byte aligned; with nblocks > 1 a stride must hold the largest
+ * block.  AG_RS_ERR_INVALID_ARGUMENT otherwise, and nothing is written. */
+int ag_block_tree_batch(ag_rs_ctx* ctx, size_t nblocks, const uint32_t* count, const uint8_t* slice_roots,
+                        uint8_t* block_hashes, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
+                        size_t proofs_stride);
+/* Repair responses (repair.rs:362-393): check_proof (merkle.rs:374-387), or with last[t] != 0
+ * check_proof_last (:394-407, 436-452: every right-hand sibling must be EMPTY_ROOTS[its height]),
+ * for n slice roots.  Item t: the root at slice_roots + t*roots_stride, index[t], the block hash
+ * at block_hashes + t*hashes_stride, proof_len[t] digests at proofs + t*proofs_stride (index,
+ * proof_len, last: device arrays; last nullable = all 0).  ok[t] = 1 / 0; proof_len[t] > 32 or
+ * 32*proof_len[t] > proofs_stride gives 0 without reading the proof.  The index is consumed one
+ * bit per proof entry; higher bits are ignored, as in the reference.  block_hashes, proofs and
+ * their strides must be 16-byte aligned. */
+int ag_block_proof_check_batch(ag_rs_ctx* ctx, size_t n, const uint8_t* slice_roots, size_t roots_stride,
+                               const uint32_t* index, const uint8_t* block_hashes, size_t hashes_stride,
+                               const uint8_t* proofs, size_t proofs_stride, const uint32_t* proof_len,
+                               const uint8_t* last, uint8_t* ok);
 
 /* ---- 6. all-or-nothing payload transforms (AONT / PETS shredders) ---------------------
  * AontShredder::shred (shredder.rs:463-470): payload := AES-128-CTR_key(payload) ||
