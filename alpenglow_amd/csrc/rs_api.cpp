@@ -4274,4 +4274,179 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   return AG_RS_OK;
 }
 
+// ---- mixed shred sizes (ag_rs_coder_*_batch_var; kernels in rs_var.hip) -------------------
+namespace {
+// batches whose column table fits 32-bit column indices (16 columns per slice at most)
+constexpr size_t kVarMaxSlices = size_t{1} << 27;
+
+// sizes[0 .. n) and the column prefix col_base[0 .. n] (cols_b = ceil(S_b / 64)) behind it
+void var_column_table(const uint32_t* S, size_t n, uint32_t* sizes, uint32_t* col_base) {
+  uint32_t cols = 0;
+  for (size_t b = 0; b < n; ++b) {
+    sizes[b] = S[b];
+    col_base[b] = cols;
+    cols += (S[b] + 63) / 64;
+  }
+  col_base[n] = cols;
+}
+
+// S of ReedSolomonCoder::shred for a payload of len bytes (reed_solomon.rs:94-95)
+size_t var_shred_size(size_t len) { return (len + 2 * kDataShreds - len % (2 * kDataShreds)) / kDataShreds; }
+
+// the slow path hands runs of consecutive equal S_b to the uniform call: the end of b's run
+size_t var_run_end(const uint32_t* S, size_t n, size_t b) {
+  size_t e = b + 1;
+  while (e < n && S[e] == S[b]) ++e;
+  return e;
+}
+}  // namespace
+
+int ag_rs_coder_shred_bytes(size_t len, size_t* shred_bytes) {
+  if (!shred_bytes) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (len > kMaxPayload) return AG_RS_ERR_TOO_MUCH_DATA;
+  *shred_bytes = var_shred_size(len);
+  return AG_RS_OK;
+}
+
+int ag_rs_coder_shred_batch_var(ag_rs_ctx* c, size_t m, size_t n, const uint8_t* payloads, size_t payload_stride,
+                                const uint32_t* lens, uint8_t* cw, size_t cw_stride, uint32_t* shred_bytes_out) {
+  if (!c || (n && (!lens || !cw))) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (m == 0 || m > kTotalShreds) return AG_RS_ERR_UNSUPPORTED_SHARD_COUNT;
+  if (n == 0) return AG_RS_OK;
+  if (n > kVarMaxSlices) return AG_RS_ERR_INVALID_ARGUMENT;
+  size_t max_s = 0;
+  for (size_t b = 0; b < n; ++b) {
+    if (lens[b] > kMaxPayload) return AG_RS_ERR_TOO_MUCH_DATA;
+    max_s = std::max(max_s, var_shred_size(lens[b]));
+  }
+  if (cw_stride < (kDataShreds + m) * max_s) return AG_RS_ERR_INVALID_ARGUMENT;
+  int st = c->enter();
+  if (st) return st;
+  // lens | sizes | col_base through the lengths' pinned staging, rewritten once its last upload
+  // has completed (ag_rs_coder_shred_batch)
+  if (c->lens_ev) AG_HIP(hipEventSynchronize(c->lens_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->lens_ev, hipEventDisableTiming));
+  const size_t words = 3 * n + 1;
+  if ((st = c->h_lens.ensure(words * 4))) return st;
+  uint32_t* h = c->h_lens.as<uint32_t>();
+  std::memcpy(h, lens, n * 4);
+  for (size_t b = 0; b < n; ++b) h[n + b] = static_cast<uint32_t>(var_shred_size(lens[b]));
+  var_column_table(h + n, n, h + n, h + 2 * n);
+  if (shred_bytes_out) std::memcpy(shred_bytes_out, h + n, n * 4);
+  c->last_encode_kernels = 0;
+  if (m != kDataShreds || odd_layout(cw, cw, cw_stride, cw_stride)) {
+    const std::vector<uint32_t> S(h + n, h + 2 * n);  // (the uniform calls reuse the staging)
+    for (size_t b = 0, e; b < n; b = e) {
+      e = var_run_end(S.data(), n, b);
+      if ((st = ag_rs_coder_shred_batch(c, m, e - b, S[b], payloads ? payloads + b * payload_stride : nullptr,
+                                        payload_stride, lens + b, cw + b * cw_stride, cw_stride)))
+        return st;
+    }
+    return AG_RS_OK;
+  }
+  if ((st = c->d_lens.ensure(words * 4, c->stream))) return st;
+  AG_HIP(hipMemcpyAsync(c->d_lens.ptr, h, words * 4, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->lens_ev, c->stream));
+  const uint32_t* d = c->d_lens.as<uint32_t>();
+  if (ag::launch_var_pad(payloads, payload_stride, d, d + n, cw, cw_stride, n, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  ag::VarParams p{};
+  p.cw = cw;
+  p.stride = cw_stride;
+  p.sizes = d + n;
+  p.col_base = d + 2 * n;
+  p.nslices = static_cast<uint32_t>(n);
+  p.total_columns = h[3 * n];
+  c->last_encode_kernels |= ag::kEkVar;
+  return ag::launch_var_encode(p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+}
+
+int ag_rs_coder_deshred_batch_var(ag_rs_ctx* c, size_t m, size_t n, const uint32_t* S, uint8_t* cw, size_t cw_stride,
+                                  const uint8_t* dpres, const uint8_t* cpres, int mode, int64_t* out) {
+  if (!c || (n && (!S || !cw || !dpres || !cpres || !out))) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (m == 0 || m > kTotalShreds) return AG_RS_ERR_UNSUPPORTED_SHARD_COUNT;
+  if (mode != AG_RS_DECODE_EXACT && mode != AG_RS_DECODE_ANY_K) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return AG_RS_OK;
+  if (n > kVarMaxSlices) return AG_RS_ERR_INVALID_ARGUMENT;
+  size_t max_s = 0;
+  for (size_t b = 0; b < n; ++b) {
+    if (S[b] == 0 || S[b] % 2) return AG_RS_ERR_INVALID_SHARD_SIZE;
+    if (kDataShreds * S[b] > kMaxAfterPadding) return AG_RS_ERR_TOO_MUCH_DATA;  // reed_solomon.rs:183
+    max_s = std::max<size_t>(max_s, S[b]);
+  }
+  if (cw_stride < (kDataShreds + m) * max_s) return AG_RS_ERR_INVALID_ARGUMENT;
+  int st = c->enter();
+  if (st) return st;
+  c->last_encode_kernels = 0;
+  c->last_window_kernels = 0;
+  auto fallback = [&]() {
+    uint32_t ek = 0, wk = 0;  // (each uniform call resets the records)
+    int r = AG_RS_OK;
+    for (size_t b = 0, e; b < n && !r; b = e) {
+      e = var_run_end(S, n, b);
+      r = ag_rs_coder_deshred_batch(c, m, e - b, S[b], cw + b * cw_stride, cw_stride, dpres + b * kDataShreds,
+                                    cpres + b * m, mode, out + b);
+      ek |= c->last_encode_kernels;
+      wk |= c->last_window_kernels;
+    }
+    c->last_encode_kernels = ek;
+    c->last_window_kernels = wk;
+    return r;
+  };
+  if (m != kDataShreds || odd_layout(cw, cw, cw_stride, cw_stride)) return fallback();
+  // present words | sizes | col_base, packed straight into the present words' pinned staging
+  // (ag_rs_coder_deshred_batch's device-pattern path)
+  if (c->present_ev) AG_HIP(hipEventSynchronize(c->present_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->present_ev, hipEventDisableTiming));
+  const size_t bytes = 8 * n + 4 * (2 * n + 1);
+  if ((st = c->h_present.ensure(bytes))) return st;
+  uint64_t* pres = c->h_present.as<uint64_t>();
+  bool full_data = false;
+  const bool surplus = pack_present_words(dpres, cpres, m, n, pres, &full_data);
+  // EXACT with surplus shreds: the crate's decoder reads every kept shred (the uniform call's host path)
+  if (mode != AG_RS_DECODE_ANY_K && surplus) return fallback();
+  uint32_t* h = reinterpret_cast<uint32_t*>(pres + n);
+  var_column_table(S, n, h, h + n);
+  if ((st = c->d_present.ensure(bytes, c->stream))) return st;
+  AG_HIP(hipMemcpyAsync(c->d_present.ptr, pres, bytes, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->present_ev, c->stream));
+  const uint64_t* d_present = c->d_present.as<uint64_t>();
+  const uint32_t* d = reinterpret_cast<const uint32_t*>(d_present + n);
+  // pipe_coder_enqueue's stages over the column table: patterns and locator constants (they do
+  // not depend on S), the window decode with the fused coding restore, the strip, the store
+  // masks, the re-encode
+  if ((st = pipe_coder_reserve(c, n, kDataShreds))) return st;
+  uint64_t* xm = c->d_xmask.as<uint64_t>();
+  uint32_t* rows = c->d_rows.as<uint32_t>();
+  uint8_t* few = c->d_pipe_few.as<uint8_t>();
+  uint64_t* mask = c->d_pipe_mask.as<uint64_t>();
+  int64_t* strip = c->d_strip.as<int64_t>();
+  if (ag::launch_pipe_patterns(d_present, n, xm, few, true, c->stream) != hipSuccess ||
+      ag::launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), 64, c->dtables(), rows, true, c->stream) !=
+          hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  ag::VarParams p{};
+  p.cw = cw;
+  p.stride = cw_stride;
+  p.sizes = d;
+  p.col_base = d + n;
+  p.nslices = static_cast<uint32_t>(n);
+  p.total_columns = h[2 * n];
+  p.pmask = xm + n;
+  p.rows = rows;
+  c->last_window_kernels |= ag::kDxVar;
+  if (ag::launch_var_decode(p, c->stream) != hipSuccess ||
+      ag::launch_var_strip(cw, cw_stride, d, n, strip, c->stream) != hipSuccess ||
+      ag::launch_pipe_store_masks(few, strip, d_present, 1, n, mask, -AG_RS_ERR_NOT_ENOUGH_SHARDS,
+                                  -AG_RS_ERR_INVALID_PADDING, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  // no surplus and no slice with every data shred: every store mask is zero (pipe_coder_enqueue)
+  if (surplus || full_data) {
+    p.out_mask = mask;
+    c->last_encode_kernels |= ag::kEkVar;
+    if (ag::launch_var_encode(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  }
+  return pipe_coder_finish(c, n, out);  // synchronous
+}
+
 }  // extern "C"

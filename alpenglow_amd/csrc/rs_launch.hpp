@@ -44,6 +44,7 @@ enum EncodeKernelBit : uint32_t {
   kEkLowRate2 = 1u << 5,  // xform_h8 LR2: two LowRate chunks of a 32-point code
   kEkGeneric = 1u << 6,   // generic_encode_kernel (table-driven)
   kEkRestride = 1u << 7,  // tail bytes restrided through padded shards
+  kEkVar = 1u << 8,       // var_encode_kernel: mixed shred sizes over the column table (rs_var.hip)
 };
 // The 32-point encode kernel launch_xform(kEncode32, p) runs: xform8 for batches of fewer
 // than 256 tiles and for 8 / 16 KiB shards (chunks_per_shard 128 / 256), else xform<4>.
@@ -187,7 +188,8 @@ struct DecodeXParams {
 // W = 32 / 64: pass 0.  W = 128: pass 1 (the other half's inputs, raw partial outputs), then
 // pass 2 (the output half's inputs, the partial added, output multiply); masks per pass.
 // which (optional): ORed with the DecodeXKernelBit of the W = 64 kernel launched (test aid)
-enum DecodeXKernelBit : uint32_t { kDxPkFused = 1, kDxPk = 2, kDxH8Fused = 4, kDxH8 = 8, kDxX16 = 16 };
+// (kDxVar: var_decode_kernel, the mixed-size window decode of rs_var.hip)
+enum DecodeXKernelBit : uint32_t { kDxPkFused = 1, kDxPk = 2, kDxH8Fused = 4, kDxH8 = 8, kDxX16 = 16, kDxVar = 32 };
 hipError_t launch_decode_x(unsigned W, int pass, const DecodeXParams& p, uint64_t ntiles, hipStream_t stream,
                            uint32_t* which = nullptr);
 hipError_t launch_decode_rows128(const uint64_t* m6, uint32_t npat, const GfDeviceTables& t, uint32_t* rows,
@@ -290,6 +292,33 @@ hipError_t launch_coder_pad(const uint8_t* payload, uint64_t payload_stride, con
                             uint64_t cw_stride, uint32_t data_bytes, uint64_t nslices, hipStream_t stream);
 hipError_t launch_coder_strip(const uint8_t* cw, uint64_t cw_stride, uint32_t data_bytes, uint64_t nslices,
                               int64_t* out, hipStream_t stream);
+
+// ReedSolomonCoder batches of slices with their own shred sizes (rs_var.hip; RegularShredder's
+// 32:32).  Slice b's codeword starts at cw + b * stride: 32 data shards then 32 coding shards
+// of sizes[b] bytes each.  The kernels run over the batch's columns (64-byte chunks of a
+// shard, the last one of a slice its tail of sizes[b] % 64 bytes when that is not zero):
+// col_base[b] = columns before slice b, col_base[nslices] = total_columns.
+struct VarParams {
+  uint8_t* cw;
+  uint64_t stride;
+  const uint32_t* col_base;  // device, nslices + 1
+  const uint32_t* sizes;     // device, nslices: S_b (even, 2 .. 1024)
+  uint32_t nslices;
+  uint32_t total_columns;
+  const uint64_t* out_mask;  // encode: per slice, bit s set => coding shard s is stored (null: all)
+  const uint64_t* pmask;     // decode: [slice][2] window positions loaded, positions restored
+  const uint32_t* rows;      // decode: [slice][64] polynomial-basis locator constants
+};
+// padding writer (payload null = in place) and padding strip (out[b] = payload length or -1)
+// over the data regions 32 * sizes[b]
+hipError_t launch_var_pad(const uint8_t* payload, uint64_t payload_stride, const uint32_t* lens, const uint32_t* sizes,
+                          uint8_t* cw, uint64_t cw_stride, uint64_t nslices, hipStream_t stream);
+hipError_t launch_var_strip(const uint8_t* cw, uint64_t cw_stride, const uint32_t* sizes, uint64_t nslices,
+                            int64_t* out, hipStream_t stream);
+// the 32-point HighRate encode of every column (data shards -> coding shards, in place)
+hipError_t launch_var_encode(const VarParams& p, hipStream_t stream);
+// the W = 64 per-lane window decode with the fused coding restore (launch_pipe_patterns' masks)
+hipError_t launch_var_decode(const VarParams& p, hipStream_t stream);
 
 // Synthetic blocks: splitmix64 u64 little-endian words, block b seeded seed_base + b.
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t nblocks, uint64_t block_bytes,

@@ -75,6 +75,7 @@ EXPORTS = (
     "ag_rs_coder_new", "ag_rs_coder_free", "ag_rs_coder_num_coding", "ag_rs_coder_shred", "ag_rs_coder_deshred",
     "ag_rs_encoder_new_on_device", "ag_rs_decoder_new_on_device", "ag_rs_coder_new_on_device",
     "ag_rs_coder_shred_batch", "ag_rs_coder_deshred_batch",
+    "ag_rs_coder_shred_bytes", "ag_rs_coder_shred_batch_var", "ag_rs_coder_deshred_batch_var",
     "ag_merkle_empty_root", "ag_merkle_height", "ag_merkle_node_count", "ag_merkle_build_batch",
     "ag_merkle_verify_batch", "ag_block_tree_batch", "ag_block_proof_check_batch",
     "ag_aes128_encrypt_block", "ag_cipher_apply_keystream_batch", "ag_sha256_batch", "ag_aon_encrypt_batch",
@@ -147,6 +148,9 @@ def load():
         "ag_rs_coder_deshred": ([p, sz, p, p, p, p, psz, p, p, psz], i),
         "ag_rs_coder_shred_batch": ([p, sz, sz, sz, p, sz, p, p, sz], i),
         "ag_rs_coder_deshred_batch": ([p, sz, sz, sz, p, sz, p, p, i, p], i),
+        "ag_rs_coder_shred_bytes": ([sz, psz], i),
+        "ag_rs_coder_shred_batch_var": ([p, sz, sz, p, sz, p, p, sz, p], i),
+        "ag_rs_coder_deshred_batch_var": ([p, sz, sz, p, p, sz, p, p, i, p], i),
         "ag_merkle_empty_root": ([sz, p], i),
         "ag_merkle_height": ([sz], sz),
         "ag_merkle_node_count": ([sz], sz),
@@ -372,6 +376,54 @@ def coder_deshred_batch(ctx: Context, num_coding: int, nslices: int, shred_bytes
     return [int(v) if v >= 0 else STATUS_KIND.get(int(-v), f"Status{int(-v)}") for v in out]
 
 
+def coder_shred_bytes(payload_len: int) -> int:
+    """The shred size ReedSolomonCoder::shred gives a payload of ``payload_len`` bytes (host only)."""
+    out = ctypes.c_size_t(0)
+    _check(load().ag_rs_coder_shred_bytes(payload_len, ctypes.byref(out)), "ag_rs_coder_shred_bytes")
+    return out.value
+
+
+def coder_shred_batch_var(ctx: Context, num_coding: int, nslices: int, payloads, payload_stride: int, payload_lens,
+                          codewords, codeword_stride: int):
+    """``coder_shred_batch`` for slices of mixed shred sizes: slice b's size follows from
+    payload_lens[b], its codeword (32 data + num_coding coding shards, packed with that size) is at
+    codewords + b * codeword_stride.  Returns the shred sizes (numpy u32)."""
+    import numpy as np
+
+    lens = np.ascontiguousarray(np.asarray(payload_lens, dtype=np.uint32))
+    if lens.size != nslices:
+        raise ValueError("payload_lens does not match the batch")
+    out = np.zeros(nslices, np.uint32)
+    _check(load().ag_rs_coder_shred_batch_var(ctx.handle, num_coding, nslices,
+                                              _ptr(payloads) if payloads is not None else None, payload_stride,
+                                              lens.ctypes.data, _ptr(codewords), codeword_stride, out.ctypes.data),
+           "ag_rs_coder_shred_batch_var")
+    return out
+
+
+def coder_deshred_batch_var(ctx: Context, num_coding: int, nslices: int, shred_bytes, codewords,
+                            codeword_stride: int, data_present, coding_present,
+                            mode: int = DECODE_EXACT, as_array: bool = False):
+    """``coder_deshred_batch`` for slices of mixed shred sizes (shred_bytes: one per slice)."""
+    import numpy as np
+
+    sizes = np.ascontiguousarray(np.asarray(shred_bytes, dtype=np.uint32))
+    dp = np.ascontiguousarray(np.frombuffer(bytes(data_present), np.uint8) if isinstance(data_present, (bytes, bytearray))
+                              else np.asarray(data_present, dtype=np.uint8))
+    cp = np.ascontiguousarray(np.frombuffer(bytes(coding_present), np.uint8) if isinstance(coding_present, (bytes, bytearray))
+                              else np.asarray(coding_present, dtype=np.uint8))
+    if sizes.size != nslices or dp.size != nslices * 32 or cp.size != nslices * num_coding:
+        raise ValueError("shred sizes / present-flag arrays do not match the batch")
+    out = np.empty(nslices, np.int64)
+    _check(load().ag_rs_coder_deshred_batch_var(ctx.handle, num_coding, nslices, sizes.ctypes.data, _ptr(codewords),
+                                                codeword_stride, dp.ctypes.data, cp.ctypes.data, mode,
+                                                out.ctypes.data),
+           "ag_rs_coder_deshred_batch_var")
+    if as_array:
+        return out
+    return [int(v) if v >= 0 else STATUS_KIND.get(int(-v), f"Status{int(-v)}") for v in out]
+
+
 DECODE_CLASSES = {0: "none", 1: "transform", 2: "generic", 3: "window64", 4: "syndrome", 5: "lowrate_chunk",
                   6: "correction", 8: "window128", 9: "server_window64"}
 
@@ -385,22 +437,23 @@ def last_decode_classes(ctx: Context) -> dict:
     return {DECODE_CLASSES.get(i, str(i)): int(v) for i, v in enumerate(out) if v}
 
 
-ENCODE_KERNELS = ("xform4", "xform8", "xform_h8", "encode_mc", "lowrate", "lowrate2", "generic", "restride")
+ENCODE_KERNELS = ("xform4", "xform8", "xform_h8", "encode_mc", "lowrate", "lowrate2", "generic", "restride",
+                  "var_encode")
 
 
 def last_encode_kernels(ctx: Context) -> set:
-    """The encode kernels the last ``encode_batch`` or ``coder_deshred_batch`` (its re-encode) on
-    ``ctx`` launched (test aid; the bits of ``ag::EncodeKernelBit``, rs_launch.hpp)."""
+    """The encode kernels the last ``encode_batch``, ``coder_deshred_batch`` (its re-encode),
+    ``coder_shred_batch_var`` or ``coder_deshred_batch_var`` on ``ctx`` launched (test aid; the bits of ``ag::EncodeKernelBit``, rs_launch.hpp)."""
     out = ctypes.c_uint32(0)
     _check(load().ag_rs_internal_last_encode_kernels(ctx.handle, ctypes.byref(out)), "last_encode_kernels")
     return {name for i, name in enumerate(ENCODE_KERNELS) if out.value >> i & 1}
 
 
-WINDOW_KERNELS = ("decode_pk_fused", "decode_pk", "decode_h8_fused", "decode_h8", "decode_x16")
+WINDOW_KERNELS = ("decode_pk_fused", "decode_pk", "decode_h8_fused", "decode_h8", "decode_x16", "var_decode")
 
 
 def last_window_kernels(ctx: Context) -> set:
-    """The W = 64 window kernels the last ``coder_deshred_batch`` on ``ctx`` launched (test aid;
+    """The W = 64 window kernels the last ``coder_deshred_batch`` / ``_var`` on ``ctx`` launched (test aid;
     the bits of ``ag::DecodeXKernelBit``, rs_launch.hpp)."""
     out = ctypes.c_uint32(0)
     _check(load().ag_rs_internal_last_window_kernels(ctx.handle, ctypes.byref(out)), "last_window_kernels")

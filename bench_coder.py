@@ -10,6 +10,13 @@ ag_rs_coder_deshred_batch with every data shred absent (ANY_K by default; --exac
 crate decoder).  Device-resident codewords (64 KiB per slice).  Prints one JSON line:
 slices/s, payload GiB/s, per-call ms, and a CPU baseline (the C oracle: pad + encode,
 decode + re-encode, 16 threads, bounded sample).
+
+--mixed-sizes: a block's real mix of shred sizes (80 % full slices, S uniform over 1008, 1010,
+.. 1024; 20 % timed-out slices, S uniform over the even sizes 2 .. 1006; seeded) through
+ag_rs_coder_shred_batch_var / ag_rs_coder_deshred_batch_var, the deshred from a random 32 of
+the 64 shreds per slice.  With --presorted-uniform the same population goes the old way: already
+sorted and compacted by size, one uniform call per distinct size (the caller's gather and
+scatter are not timed).  One JSON line: slices/s of the shred and of the deshred.
 """
 from __future__ import annotations
 
@@ -22,6 +29,128 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 GIB = float(1 << 30)
+
+
+def mixed_sizes(n: int, seed: int = 0xB10C):
+    """Seeded shred sizes of a block's slices: 80 % full (1008 .. 1024), 20 % timed out (2 .. 1006)."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    full = 1008 + 2 * rng.integers(0, 9, n)
+    short = 2 + 2 * rng.integers(0, 503, n)
+    return np.where(rng.random(n) < 0.8, full, short).astype(np.uint32)
+
+
+def run_mixed(args):
+    import numpy as np
+    import torch
+
+    from alpenglow_amd import rs
+
+    dev = torch.device("cuda:0")
+    ctx = rs.Context(0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)
+    n, m = args.slices, 32
+    sizes = mixed_sizes(n)
+    lens = (32 * sizes - 1).astype(np.uint32)  # the longest payload of each size
+    rng = np.random.default_rng(0xA221)
+    arrived = np.argsort(rng.random((n, 64)), axis=1)[:, :32]  # first 32 arrivals per slice
+    present = np.zeros((n, 64), np.uint8)
+    np.put_along_axis(present, arrived, 1, axis=1)
+    dpres, cpres = np.ascontiguousarray(present[:, :32]), np.ascontiguousarray(present[:, 32:])
+    mode = rs.DECODE_EXACT if args.exact else rs.DECODE_ANY_K
+    distinct = np.unique(sizes)
+    groups = [np.flatnonzero(sizes == S) for S in distinct]
+    if args.presorted_uniform:
+        bufs = []
+        for S, idx in zip(distinct, groups):
+            S = int(S)
+            b = torch.empty((len(idx), 64 * S), dtype=torch.uint8, device=dev)
+            rs.fill_splitmix(ctx, b, len(idx), 32 * S, 64 * S, 0xC0DE0000 + S)
+            bufs.append((S, len(idx), b, lens[idx], np.ascontiguousarray(dpres[idx]), np.ascontiguousarray(cpres[idx])))
+
+        def shred():
+            for S, cnt, b, ln, _, _ in bufs:
+                rs.coder_shred_batch(ctx, m, cnt, S, None, 0, ln, b, 64 * S)
+
+        def deshred():
+            return np.concatenate([rs.coder_deshred_batch(ctx, m, cnt, S, b, 64 * S, dp, cp, mode=mode, as_array=True)
+                                   for S, cnt, b, _, dp, cp in bufs])
+
+        want_lens = np.concatenate([ln for _, _, _, ln, _, _ in bufs])
+    else:
+        stride = 64 * 1024
+        cw = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+        rs.fill_splitmix(ctx, cw, n, 32 * 1024, stride, 0xC0DE0000)  # payload bytes in the data regions
+
+        def shred():
+            rs.coder_shred_batch_var(ctx, m, n, None, 0, lens, cw, stride)
+
+        def deshred():
+            return rs.coder_deshred_batch_var(ctx, m, n, sizes, cw, stride, dpres, cpres, mode=mode, as_array=True)
+
+        want_lens = lens
+    shred()
+    for _ in range(args.warmup):
+        shred()
+        deshred()
+    torch.cuda.synchronize()
+    t_sh = t_de = 0.0
+    for _ in range(args.steps):
+        a = time.perf_counter()
+        shred()
+        torch.cuda.synchronize()
+        b = time.perf_counter()
+        res = deshred()  # synchronous
+        c = time.perf_counter()
+        t_sh += b - a
+        t_de += c - b
+    ok = bool((res == want_lens).all())
+    verify = {"all_slices_restored": ok}
+    if not args.presorted_uniform:
+        # zero every absent shred, deshred once more, compare with the shredded codewords; spot
+        # check the smallest, a middle and the largest slice against the oracle's coder
+        want = cw.clone()
+        pres = torch.from_numpy(present).to(dev)
+        for S, idx in zip(distinct, groups):
+            S = int(S)
+            rows = torch.from_numpy(idx).to(dev)
+            kept = cw[rows, :64 * S].view(-1, 64, S) * pres[rows].unsqueeze(-1)
+            cw[rows, :64 * S] = kept.view(-1, 64 * S)
+        res2 = deshred()
+        verify["all_slices_restored"] = ok and bool((res2 == lens).all()) and bool(torch.equal(cw, want))
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import rs_oracle as o
+        spot = True
+        for i in (int(np.argmin(sizes)), n // 2, int(np.argmax(sizes))):
+            S, host = int(sizes[i]), cw[i].cpu().numpy()
+            raw = o.coder_shred(host[:int(lens[i])].tobytes(), m)
+            spot &= host[:64 * S].tobytes() == b"".join(raw.data) + b"".join(raw.coding)
+        verify["shreds_match_oracle"] = bool(spot)
+        verify["encode_kernels"] = sorted(rs.last_encode_kernels(ctx))
+        verify["window_kernels"] = sorted(rs.last_window_kernels(ctx))
+    how = "one uniform call per distinct size, presorted" if args.presorted_uniform else "one mixed-size call"
+    line = {
+        "metric": f"slices/s ReedSolomonCoder shred and deshred (random 32 of 64 shreds per slice), mixed shred sizes, {how}",
+        "value": n * args.steps / (t_sh + t_de),
+        "unit": "slices/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "higher_is_better": True,
+        "shred_slices_per_s": n * args.steps / t_sh,
+        "deshred_slices_per_s": n * args.steps / t_de,
+        "calls_ms": {"shred": t_sh * 1e3 / args.steps, "deshred": t_de * 1e3 / args.steps},
+        "config": {"workload": f"{n} slices, 32:32, 80 % S in 1008..1024, 20 % even S in 2..1006 "
+                               f"({len(distinct)} distinct sizes, {int(sizes.astype(np.int64).sum()) * 64} codeword bytes)",
+                   "calls_per_step": 2 * len(distinct) if args.presorted_uniform else 2,
+                   "mode": "EXACT" if args.exact else "ANY_K"},
+        "verify": verify,
+    }
+    print(json.dumps(line), flush=True)
+    ctx.close()
 
 
 def main():
@@ -41,7 +170,13 @@ def main():
                     help="payload bytes per slice (default MAX_DATA_PER_SLICE = 32767: 1 KiB shreds); the "
                          "shred size is the padded length / 32 (reed_solomon.rs:94-95), e.g. 16383 -> 512 B")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--mixed-sizes", action="store_true",
+                    help="a block's mix of shred sizes through the _var calls (see the module text)")
+    ap.add_argument("--presorted-uniform", action="store_true",
+                    help="with --mixed-sizes: the same slices sorted and compacted by size, one uniform call per size")
     args = ap.parse_args()
+    if args.mixed_sizes:
+        return run_mixed(args)
     import numpy as np
     import torch
 

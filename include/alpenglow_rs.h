@@ -213,7 +213,8 @@ int ag_rs_coder_deshred(ag_rs_coder* coder, size_t data_shreds, const uint8_t* c
                         uint8_t* coding_out, size_t* shred_bytes);
 
 /* ---- 2b. ReedSolomonCoder over batches of slices (device-resident) -------------------
- * All slices of a call share one shred size S (even, <= 1024).  Slice b's codeword is 32
+ * All slices of a call share one shred size S (even, <= 1024); the _var forms at the end of
+ * this section take one size per slice.  Slice b's codeword is 32
  * data shards then num_coding coding shards, contiguous, at codewords + b*codeword_stride
  * (stride >= (32 + num_coding) * S).  A batch form of reed_solomon.rs:88-128 / :140-208 for
  * callers holding many slices (block production, repair catch-up): the same bytes as
@@ -243,6 +244,42 @@ int ag_rs_coder_deshred_batch(ag_rs_ctx* ctx, size_t num_coding, size_t nslices,
                               size_t shred_bytes, uint8_t* codewords, size_t codeword_stride,
                               const uint8_t* data_present, const uint8_t* coding_present,
                               int mode, int64_t* payload_len_out);
+
+/* Mixed shred sizes: one call for slices that each have their own S_b (a block's slices: a
+ * full slice closes with S in 1008 .. 1024, a timed-out one with any even S).  Slice b's
+ * codeword is at codewords + b*codeword_stride -- 32 data shards then num_coding coding shards,
+ * packed with stride S_b, exactly the layout of the uniform call for that slice alone -- and
+ * its bytes and its payload_len_out value are those of ag_rs_coder_shred_batch /
+ * ag_rs_coder_deshred_batch called on it with S = S_b.  No byte of a slice's stride past
+ * (32 + num_coding) * S_b is written.
+ *
+ * S of ReedSolomonCoder::shred for a payload of payload_len bytes (reed_solomon.rs:94-95):
+ * (len + 64 - len % 64) / 32.  Host only, needs no device.  TOO_MUCH_DATA above 32767. */
+int ag_rs_coder_shred_bytes(size_t payload_len, size_t* shred_bytes);
+
+/* shred_batch_var: S_b follows from payload_lens[b] (ag_rs_coder_shred_bytes) and is
+ * returned in shred_bytes_out (HOST, nslices, may be NULL).  payloads NULL: the payloads
+ * already sit in the data regions (ag_slice_frame_batch called with shred_bytes = 1024 puts
+ * them there).  Asynchronous on the context stream.
+ * deshred_batch_var: shred_bytes (HOST, nslices) gives S_b.  Synchronous.
+ * Whole-call errors (nothing launched, outputs untouched): TOO_MUCH_DATA (a payload length
+ * > 32767, an S_b > 1024), INVALID_SHARD_SIZE (an S_b of zero or odd), INVALID_ARGUMENT
+ * (codeword_stride < (32 + num_coding) * max S_b, a null pointer with nslices > 0, a bad
+ * mode, nslices > 2^27), UNSUPPORTED_SHARD_COUNT (num_coding 0 or > 64).
+ * num_coding = 32 (RegularShredder) runs in a fixed number of launches whatever the mix of
+ * sizes, in place for every even S_b -- shred always; deshred under AG_RS_DECODE_ANY_K, and
+ * under AG_RS_DECODE_EXACT when no slice keeps more than 32 shreds.  Everything else
+ * (num_coding != 32, EXACT with surplus shreds, byte-odd codewords or strides) is handed to
+ * the uniform calls in runs of consecutive equal S_b: correct, and slow on a mixed batch. */
+int ag_rs_coder_shred_batch_var(ag_rs_ctx* ctx, size_t num_coding, size_t nslices,
+                                const uint8_t* payloads, size_t payload_stride,
+                                const uint32_t* payload_lens, uint8_t* codewords,
+                                size_t codeword_stride, uint32_t* shred_bytes_out);
+int ag_rs_coder_deshred_batch_var(ag_rs_ctx* ctx, size_t num_coding, size_t nslices,
+                                  const uint32_t* shred_bytes, uint8_t* codewords,
+                                  size_t codeword_stride, const uint8_t* data_present,
+                                  const uint8_t* coding_present, int mode,
+                                  int64_t* payload_len_out);
 
 /* ---- 4b. slice payload framing ---------------------------------------------------------
  * Slice::payload_bytes (types/slice.rs:73-84) and SlicePayload::try_from (slice.rs:211-218)
