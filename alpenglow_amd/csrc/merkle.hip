@@ -15,6 +15,7 @@
 //   merkle_leaf_kernel    one thread per leaf (all slices): SHA-256 of label || shred.
 //                         Integer VALU-bound (~1.2k VALU per 64-byte SHA-256 block and
 //                         lane: v_alignbit rotations, v_bitop3 sigma XORs / ch / maj, v_add3)
+//   merkle_leaf_var_kernel  the same with one leaf size per slice: one wave per slice
 //   merkle_level_kernel   one launch per tree level, one thread per (slice, pair)
 //   merkle_proof_kernel   one thread per leaf: its create_proof siblings
 //   merkle_verify_kernel  one thread per (leaf, index, root, proof): derive_root == root;
@@ -29,6 +30,7 @@
 
 #include "merkle.hpp"
 #include "sha256.hpp"
+#include "unaligned.hpp"
 
 namespace ag {
 
@@ -36,20 +38,30 @@ namespace {
 
 using sha::hash_pair;
 
-// SHA-256(LEAF_LABEL || data[0..len)).  A4: data is 16-byte aligned (vector loads).
+// How leaf_hash loads the leaf bytes.
+enum LeafLoad : int {
+  kLeafByte = 0,  // any address: four byte loads per SHA word
+  kLeafA16 = 1,   // data is 16-byte aligned: vector loads
+  kLeafU16 = 2,   // any address: the same vector loads through types of alignment 1 (unaligned.hpp);
+                  // the hardware splits an access that straddles, no byte loads for whole words
+};
+
+// SHA-256(LEAF_LABEL || data[0..len)).  A4 = a LeafLoad (true / false: kLeafA16 / kLeafByte).
 // The blocks made only of data bytes (b = 1 .. T/64 - 1, T = 32 + len) are software-pipelined:
 // block b + 1's four 16-byte loads are issued before block b's compression, so each lane's
 // HBM latency (its leaf is 1 KiB away from its neighbours', one cache line per lane and
 // instruction) hides under ~1.2k VALU of rounds instead of stalling every block.
-template <bool A4>
+template <int A4>
 __device__ __forceinline__ void leaf_hash(const uint8_t* __restrict__ data, uint32_t len, uint32_t out[8]) {
   uint32_t st[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) st[i] = sha::kIv[i];
   const uint32_t T = 32 + len, nblk = (T + 9 + 63) / 64;
   auto word = [&](uint32_t j) -> uint32_t {
-    if constexpr (A4) {
+    if constexpr (A4 == kLeafA16) {
       return reinterpret_cast<const uint32_t*>(data)[j];
+    } else if constexpr (A4 == kLeafU16) {
+      return ld4u(data + 4 * j);
     } else {
       return uint32_t(data[4 * j]) | (uint32_t(data[4 * j + 1]) << 8) | (uint32_t(data[4 * j + 2]) << 16) |
              (uint32_t(data[4 * j + 3]) << 24);
@@ -62,12 +74,15 @@ __device__ __forceinline__ void leaf_hash(const uint8_t* __restrict__ data, uint
     for (int i = 0; i < 16; ++i) w[i] = sha::leaf_msg_word(16 * b + i, len, nblk, word, byte);
     sha::compress(st, w);
   };
-  if constexpr (A4) {
+  if constexpr (A4 != kLeafByte) {
     const uint32_t nd = T / 64;  // blocks 1 .. nd - 1 are data only (words 16 b - 8 ..)
     uint4 nx[4];
     auto fetch = [&](uint32_t b) __attribute__((always_inline)) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) nx[q] = *reinterpret_cast<const uint4*>(data + 64 * b - 32 + 16 * q);
+      for (int q = 0; q < 4; ++q) {
+        if constexpr (A4 == kLeafU16) nx[q] = ld16u(data + 64 * b - 32 + 16 * q);
+        else nx[q] = *reinterpret_cast<const uint4*>(data + 64 * b - 32 + 16 * q);
+      }
     };
     if (nd > 1) fetch(1);
     generic(0);
@@ -145,6 +160,25 @@ __global__ __launch_bounds__(256) void merkle_leaf_kernel(const MerkleBuildParam
   leaf_hash<A4>(p.leaves + s * p.slice_stride + jr * p.leaf_stride, p.leaf_bytes, h);
   store_digest(nodes + s * nodes_stride + 32 * j, h);
   if (p.n_leaves == 1) store_digest(p.roots + 32 * s, h);  // a one-leaf tree's root is the leaf
+}
+
+// Level 0 with one leaf size per slice (p.leaf_sizes): one wave per slice, a lane per leaf, so
+// the size is wave-uniform (a scalar: the block loops of leaf_hash branch on it without
+// divergence) and a wave's 64 rows are one contiguous run of 64 * size bytes.  Rows sit at
+// j * size: 16-byte aligned for every j only when size % 16 == 0, 2-byte aligned otherwise.
+// One loader serves both: kLeafU16 issues the aligned path's global_load_dwordx4 / _dword at
+// whatever address the row has (an aligned row costs what it costs in merkle_leaf_kernel<true>;
+// a straddling access is split by the memory pipeline, not by byte loads in the shader).
+__global__ __launch_bounds__(256) void merkle_leaf_var_kernel(const MerkleBuildParams p, uint8_t* nodes,
+                                                              uint64_t nodes_stride) {
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t s = static_cast<uint64_t>(blockIdx.x) * 4 + wave;
+  if (s >= p.nslices) return;
+  const uint32_t j = threadIdx.x & 63;
+  const uint32_t len = __builtin_amdgcn_readfirstlane(p.leaf_sizes[s]);
+  uint32_t h[8];
+  leaf_hash<kLeafU16>(p.leaves + s * p.slice_stride + static_cast<uint64_t>(j) * len, len, h);
+  store_digest(nodes + s * nodes_stride + 32 * j, h);
 }
 
 __global__ __launch_bounds__(256) void merkle_level_kernel(const MerkleBuildParams p, uint8_t* nodes,
@@ -426,14 +460,18 @@ hipError_t launch_block_tree(const BlockTreeParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_merkle_build(const MerkleBuildParams& p, uint8_t* nodes, uint64_t nodes_stride,
-                               hipStream_t stream) {
+                               hipStream_t stream, uint32_t* leaf_kernels) {
   if (p.nslices == 0) return hipSuccess;
   if (p.n_leaves == 0 || p.n_leaves > kMerkleMaxLeaves || !nodes || nodes_stride % 16) return hipErrorInvalidValue;
+  if (p.leaf_sizes && (p.n_leaves != kMerkleMaxLeaves || p.hash_leaf || p.skip_leaf)) return hipErrorInvalidValue;
   auto grid_of = [](uint64_t threads) { return dim3(static_cast<unsigned>((threads + 255) / 256)); };
   if ((p.nslices * p.n_leaves + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
   const bool a16 = (reinterpret_cast<uintptr_t>(p.leaves) | p.leaf_stride | p.slice_stride) % 16 == 0;
   const dim3 g0 = grid_of(p.nslices * p.n_leaves);
-  if (p.hash_leaf && p.list) {  // only the flagged leaves: compacted, so no lane idles on a known one
+  if (leaf_kernels) *leaf_kernels |= p.leaf_sizes ? kMkLeafVar : a16 ? kMkLeafAligned : kMkLeafByte;
+  if (p.leaf_sizes) {  // (g0: four waves, four slices, per workgroup)
+    hipLaunchKernelGGL(merkle_leaf_var_kernel, g0, dim3(256), 0, stream, p, nodes, nodes_stride);
+  } else if (p.hash_leaf && p.list) {  // only the flagged leaves: compacted, so no lane idles on a known one
     const uint64_t nl = p.nslices * p.n_leaves;
     if (nl >= 0xFFFFFFFFull || hipMemsetAsync(p.list + nl, 0, 4, stream) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_active_kernel, dim3(static_cast<unsigned>((nl + 1023) / 1024)), dim3(1024), 0, stream,

@@ -43,11 +43,23 @@ struct MerkleBuildParams {
   const uint8_t* hash_leaf;
   uint32_t* list;
   uint32_t skip_leaf;  // > 0: leaf j >= skip_leaf sits at (j + 1) * leaf_stride (a withheld row)
+  // nullable: one leaf size per slice (device [nslices], each even, 2 .. 1024).  Needs n_leaves =
+  // 64 and no hash_leaf / skip_leaf; leaf j of slice s is then leaf_sizes[s] bytes at leaves +
+  // s*slice_stride + j*leaf_sizes[s] (the var coder's packed codewords); leaf_stride and
+  // leaf_bytes are unused.  One leaf kernel for the whole batch, whatever the mix of sizes.
+  const uint32_t* leaf_sizes;
+};
+// The leaf kernel classes a build launches (leaf_kernels below; a test aid).
+enum MerkleLeafKernelBit : uint32_t {
+  kMkLeafAligned = 1u << 0,  // uniform size, every row 16-byte aligned: vector loads
+  kMkLeafByte = 1u << 1,     // uniform size, any alignment: the per-byte loader
+  kMkLeafVar = 1u << 2,      // one size per slice (leaf_sizes)
 };
 // nodes: the node digests (reference order, nodes_stride per slice; the caller's buffer or
-// scratch) -- the levels are built there.
+// scratch) -- the levels are built there.  leaf_kernels (nullable): |= the MerkleLeafKernelBit of
+// the leaf kernel launched.
 hipError_t launch_merkle_build(const MerkleBuildParams& p, uint8_t* nodes, uint64_t nodes_stride,
-                               hipStream_t stream);
+                               hipStream_t stream, uint32_t* leaf_kernels = nullptr);
 
 // check_proof for n leaves (or, with roots_out set, derive_root: the root each proof yields): leaf t at leaves + t*leaf_stride, its index index[t], the root
 // roots + t*roots_stride, height proof digests at proofs + t*proofs_stride; ok[t] = 0/1.

@@ -168,6 +168,10 @@ struct ag_rs_ctx {
   DevBuf d_corr, d_corrk, d_corrblocks;     // correction decoder: patterns, K picks, block ids
   DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
   DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
+  uint32_t last_merkle_kernels = 0;         // MerkleLeafKernelBit of the last Merkle build's leaf kernel
+  DevBuf d_leaf_sizes;                      // ag_merkle_build_batch_var: leaf size per slice
+  PinBuf h_leaf_sizes;                      // its pinned host staging
+  hipEvent_t leaf_sizes_ev = nullptr;       // recorded after its upload
   DevBuf d_block_meta;                      // block trees: first[nblocks] (u64), then count[nblocks] (u32)
   PinBuf h_block_meta;                      // its pinned host staging
   hipEvent_t block_meta_ev = nullptr;       // recorded after its upload
@@ -330,7 +334,7 @@ struct ag_rs_ctx {
     }
     for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &d_mask,
                       &d_xmask, &d_rows, &d_xblocks, &d_x128, &d_rows128, &d_syn, &d_synblocks, &d_corr, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_in, &stage_out, &stage_pad, &stage_mask, &d_slice_meta, &one_in,
-                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta})
+                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta, &d_leaf_sizes})
       b->release();
     for (DevBuf& b : pipe) b.release();
     if (present_ev) {
@@ -348,6 +352,11 @@ struct ag_rs_ctx {
       (void)hipEventDestroy(block_meta_ev);
     }
     h_block_meta.release();
+    if (leaf_sizes_ev) {
+      (void)hipEventSynchronize(leaf_sizes_ev);
+      (void)hipEventDestroy(leaf_sizes_ev);
+    }
+    h_leaf_sizes.release();
     h_strip.release();
     h_slice_meta.release();
     h_pipe_meta.release();
@@ -1449,6 +1458,15 @@ int ag_rs_internal_last_encode_kernels(ag_rs_ctx* c, uint32_t* out) {
   return AG_RS_OK;
 }
 
+// Test aid (not in the header): the leaf-kernel classes (ag::MerkleLeafKernelBit) the last Merkle
+// build on this context launched -- uniform size with aligned rows, uniform size through the byte
+// loader, or one size per slice.
+int ag_rs_internal_last_merkle_kernels(ag_rs_ctx* c, uint32_t* out) {
+  if (!c || !out) return AG_RS_ERR_INVALID_ARGUMENT;
+  *out = c->last_merkle_kernels;
+  return AG_RS_OK;
+}
+
 int ag_rs_has_fast_path(size_t k, size_t m, size_t S) {
   // shard sizes that are not whole 64-byte chunks run restrided (padded) on the same kernels
   if (S == 0 || S % 2) return 0;
@@ -1646,7 +1664,84 @@ int ag_merkle_build_batch(ag_rs_ctx* c, size_t n_leaves, size_t leaf_bytes, size
     if ((st = c->d_merkle_nodes.ensure(nslices * nodes_stride, c->stream))) return st;
     nodes = c->d_merkle_nodes.as<uint8_t>();
   }
-  return ag::launch_merkle_build(p, nodes, nodes_stride, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+  c->last_merkle_kernels = 0;
+  return ag::launch_merkle_build(p, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) == hipSuccess
+             ? AG_RS_OK
+             : AG_RS_ERR_DEVICE;
+}
+
+namespace {
+constexpr size_t kMerkleVarMaxSlices = size_t{1} << 27;  // (the var coder's limit)
+
+// ag_merkle_build_batch_var's host-side checks (sizes on the host): 0 or the status
+int merkle_var_check(size_t nslices, const uint32_t* leaf_bytes, const uint8_t* leaves, size_t slice_stride,
+                     const uint8_t* roots, const uint8_t* nodes, size_t nodes_stride, const uint8_t* proofs,
+                     size_t proofs_stride) {
+  if (!leaf_bytes || !leaves || !roots || nslices > kMerkleVarMaxSlices) return AG_RS_ERR_INVALID_ARGUMENT;
+  size_t max_s = 0;
+  for (size_t b = 0; b < nslices; ++b) {
+    if (leaf_bytes[b] == 0 || leaf_bytes[b] % 2) return AG_RS_ERR_INVALID_SHARD_SIZE;
+    if (leaf_bytes[b] > AG_RS_MAX_DATA_PER_SHRED) return AG_RS_ERR_TOO_MUCH_DATA;
+    max_s = std::max<size_t>(max_s, leaf_bytes[b]);
+  }
+  constexpr size_t n = AG_MERKLE_MAX_LEAVES;
+  if (slice_stride < n * max_s ||
+      (nodes && (nodes_stride % 16 || nodes_stride < 32 * ag_merkle_node_count(n))) ||
+      (proofs && (proofs_stride % 16 || proofs_stride < 32 * ag_merkle_height(n) * n)) ||
+      reinterpret_cast<uintptr_t>(roots) % 16 || reinterpret_cast<uintptr_t>(nodes) % 16 ||
+      reinterpret_cast<uintptr_t>(proofs) % 16)
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  return AG_RS_OK;
+}
+
+// The launches of ag_merkle_build_batch_var over sizes already on the device (d_sizes; checked by
+// the caller on the host): the composed shred hands over the table its coder stage uploaded.
+int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
+                      size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
+                      size_t proofs_stride) {
+  int st = ensure_empty_roots(c);
+  if (st) return st;
+  ag::MerkleBuildParams p{};
+  p.leaves = leaves;
+  p.slice_stride = slice_stride;
+  p.n_leaves = AG_MERKLE_MAX_LEAVES;
+  p.nslices = nslices;
+  p.empty_roots = c->d_empty_roots.as<uint32_t>();
+  p.roots = roots;
+  p.proofs = proofs;
+  p.proofs_stride = proofs_stride;
+  p.leaf_sizes = d_sizes;
+  if (!nodes) {
+    nodes_stride = (32 * ag_merkle_node_count(AG_MERKLE_MAX_LEAVES) + 255) / 256 * 256;
+    if ((st = c->d_merkle_nodes.ensure(nslices * nodes_stride, c->stream))) return st;
+    nodes = c->d_merkle_nodes.as<uint8_t>();
+  }
+  c->last_merkle_kernels = 0;
+  return ag::launch_merkle_build(p, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) == hipSuccess
+             ? AG_RS_OK
+             : AG_RS_ERR_DEVICE;
+}
+}  // namespace
+
+int ag_merkle_build_batch_var(ag_rs_ctx* c, size_t nslices, const uint32_t* leaf_bytes, const uint8_t* leaves,
+                              size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride,
+                              uint8_t* proofs, size_t proofs_stride) {
+  if (!c) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  int st = merkle_var_check(nslices, leaf_bytes, leaves, slice_stride, roots, nodes, nodes_stride, proofs,
+                            proofs_stride);
+  if (st) return st;
+  if ((st = c->enter())) return st;
+  // the sizes go up through pinned staging of their own (the coder's payload lengths keep theirs),
+  // rewritten once its last upload has completed
+  if (c->leaf_sizes_ev) AG_HIP(hipEventSynchronize(c->leaf_sizes_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->leaf_sizes_ev, hipEventDisableTiming));
+  if ((st = c->h_leaf_sizes.ensure(4 * nslices)) || (st = c->d_leaf_sizes.ensure(4 * nslices, c->stream))) return st;
+  std::memcpy(c->h_leaf_sizes.ptr, leaf_bytes, 4 * nslices);
+  AG_HIP(hipMemcpyAsync(c->d_leaf_sizes.ptr, c->h_leaf_sizes.ptr, 4 * nslices, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->leaf_sizes_ev, c->stream));
+  return merkle_var_launch(c, nslices, c->d_leaf_sizes.as<uint32_t>(), leaves, slice_stride, roots, nodes,
+                           nodes_stride, proofs, proofs_stride);
 }
 
 int ag_merkle_verify_batch(ag_rs_ctx* c, size_t n, size_t leaf_bytes, const uint8_t* leaves, size_t leaf_stride,
@@ -3057,6 +3152,14 @@ int ag_shred_serialize_batch(ag_rs_ctx* c, size_t n, const ag_shred_columns* col
              : AG_RS_ERR_DEVICE;
 }
 
+int ag_shred_datagram_bytes(size_t shred_bytes, size_t proof_len, size_t* out) {
+  if (!out || shred_bytes > ag::kMtuBytes || proof_len > ag::kMtuBytes / 32) return AG_RS_ERR_INVALID_ARGUMENT;
+  const size_t len = ag::kShredHeadBytes + shred_bytes + 64 + 8 + 32 * proof_len;
+  if (len > ag::kMtuBytes) return AG_RS_ERR_INVALID_ARGUMENT;
+  *out = len;
+  return AG_RS_OK;
+}
+
 int ag_slice_frame_batch(ag_rs_ctx* c, size_t nslices, size_t shred_bytes, const uint8_t* parent_flags,
                          const uint8_t* parent_ids, const uint8_t* data, size_t data_stride, const uint32_t* data_lens,
                          uint8_t* codewords, size_t codeword_stride, uint32_t* payload_lens_out) {
@@ -3519,6 +3622,119 @@ int ag_shredder_shred_batch(ag_rs_ctx* c, size_t nslices, size_t S, const uint8_
   return AG_RS_OK;
 }
 
+// RegularShredder::shred over slices of mixed shred sizes: the stages of ag_shredder_shred_batch,
+// each taking one size per slice -- the var coder (one launch set for the whole mix), the var
+// Merkle build over the size table the coder uploaded (d_lens: lens | sizes | column prefix; it
+// stays valid on the stream until the next coder call), the serializer with a row size per slice.
+int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* parent_flags, const uint8_t* parent_ids,
+                                const uint8_t* data, size_t data_stride, const uint32_t* data_lens,
+                                const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
+                                const uint8_t* seed, const uint8_t* pk, uint8_t* codewords, size_t codeword_stride,
+                                uint32_t* shred_bytes_out, uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets,
+                                size_t packet_stride, uint32_t* packet_lens, size_t nblocks,
+                                const uint32_t* block_counts, uint8_t* block_hashes_out) {
+  if (!c || nslices >= (size_t{1} << 24)) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return nblocks ? AG_RS_ERR_INVALID_ARGUMENT : AG_RS_OK;
+  if (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed || !pk ||
+      !codewords || !packets || !packet_lens || reinterpret_cast<uintptr_t>(codewords) % 16 || codeword_stride % 16)
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  const size_t n = nslices, N = n * ag::kPipeShreds;
+  // every check on the host, before the first launch: the framing's, the strides', the blocks'
+  std::vector<uint32_t> lens(n);
+  size_t max_s = 0, max_len = 0;
+  for (size_t b = 0; b < n; ++b) {
+    if (parent_flags[b] > 1) return AG_RS_ERR_INVALID_ARGUMENT;
+    const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
+    if (framed > AG_SLICE_MAX_DATA) return AG_RS_ERR_TOO_MUCH_DATA;
+    size_t S = 0;
+    if (ag_rs_coder_shred_bytes(framed, &S)) return AG_RS_ERR_TOO_MUCH_DATA;
+    max_s = std::max(max_s, S);
+    max_len = std::max<size_t>(max_len, data_lens[b]);
+  }
+  size_t need = 0;
+  if (ag_shred_datagram_bytes(max_s, ag::kPipeHeight, &need) || packet_stride < need ||
+      codeword_stride < ag::kPipeShreds * max_s || (max_len && (!data || (n > 1 && data_stride < max_len))))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nblocks) {
+    if (!block_counts || !block_hashes_out || reinterpret_cast<uintptr_t>(block_hashes_out) % 16 || nblocks > n)
+      return AG_RS_ERR_INVALID_ARGUMENT;
+    size_t sum = 0;
+    for (size_t b = 0; b < nblocks; ++b) {
+      if (block_counts[b] == 0 || block_counts[b] > AG_BLOCK_MAX_SLICES) return AG_RS_ERR_INVALID_ARGUMENT;
+      sum += block_counts[b];
+    }
+    if (sum != n) return AG_RS_ERR_INVALID_ARGUMENT;
+  }
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  // 1. Slice::payload_bytes into the data regions (a framed payload is shorter than 32 * S_s, so
+  //    it stays inside its own slice's data shreds), 2. ReedSolomonCoder::shred in place
+  int st = ag_slice_frame_batch(c, n, max_s, parent_flags, parent_ids, data, data_stride, data_lens, codewords,
+                                codeword_stride, lens.data());
+  if (st) return st;
+  if ((st = ag_rs_coder_shred_batch_var(c, ag::kPipeShreds - ag::kPipeData, n, nullptr, 0, lens.data(), codewords,
+                                        codeword_stride, shred_bytes_out)))
+    return st;
+  if (!(c->last_encode_kernels & ag::kEkVar)) return AG_RS_ERR_DEVICE;  // (16-byte-aligned codewords: always var)
+  const uint32_t* d_sizes = c->d_lens.as<uint32_t>() + n;
+  // 3. slice Merkle trees: roots and every shred's path
+  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kind, *sidx, *dlen, *height;
+  if (!roots && (st = pipe_buf(c, 0, 32 * n, &roots))) return st;
+  if (!sigs && (st = pipe_buf(c, 1, 64 * n, &sigs))) return st;
+  if ((st = pipe_buf(c, 2, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, 3, N, &kind)) ||
+      (st = pipe_buf(c, 4, 4 * N, &sidx)) || (st = pipe_buf(c, 5, 4 * N, &dlen)) ||
+      (st = pipe_buf(c, 6, 4 * N, &height)))
+    return st;
+  if ((st = merkle_var_launch(c, n, d_sizes, codewords, codeword_stride, roots, nullptr, 0, proofs,
+                              ag::kPipeShreds * kPipeProofBytes)))
+    return st;
+  // 4. slice_sig = sign(SliceCommitment(header, root)), on the side stream while 5 serializes
+  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
+  // 5. the 64 datagrams per slice, rows and data lengths at the slice's own size
+  ag::PipeExpandParams ep{};
+  ep.nslices = n;
+  ep.num_data = ag::kPipeData;
+  ep.kind = kind;
+  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
+  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
+  ep.height = reinterpret_cast<uint32_t*>(height);
+  ep.slice_bytes = d_sizes;
+  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(c->side);
+    return AG_RS_ERR_DEVICE;
+  }
+  ag::ShredColumns cols{};
+  cols.kind = kind;
+  cols.slot = const_cast<uint64_t*>(slots);
+  cols.slice_index = const_cast<uint64_t*>(slice_indices);
+  cols.is_last = const_cast<uint8_t*>(is_last);
+  cols.shred_index = ep.shred_index;
+  cols.data = codewords;
+  cols.data_stride = AG_RS_MAX_DATA_PER_SHRED;
+  cols.group_stride = codeword_stride;
+  cols.row_sizes = d_sizes;
+  cols.data_len = ep.data_len;
+  cols.sig = sigs;
+  cols.proof = proofs;
+  cols.proof_stride = kPipeProofBytes;
+  cols.height = ep.height;
+  cols.hdr_group = ag::kPipeShreds;
+  cols.skip_sig = 1;
+  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess) {
+    (void)hipStreamSynchronize(c->side);
+    return AG_RS_ERR_DEVICE;
+  }
+  // 6. the block hashes over the roots: a chain of dependent levels a few workgroups wide, placed
+  //    where the main stream would otherwise only wait for the signatures
+  if (nblocks && (st = ag_block_tree_batch(c, nblocks, block_counts, roots, block_hashes_out, nullptr, 0, nullptr, 0))) {
+    (void)hipStreamSynchronize(c->side);
+    return st;
+  }
+  AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
+  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  return AG_RS_OK;
+}
+
 int ag_shredder_deshred_batch(ag_rs_ctx* c, size_t nslices, size_t S, uint8_t* packets, size_t packet_stride,
                               uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords, int32_t* status,
                               uint64_t* slots_out, uint64_t* slice_indices_out, uint8_t* is_last_out,
@@ -3714,7 +3930,9 @@ int ag_shredder_deshred_batch(ag_rs_ctx* c, size_t nslices, size_t S, uint8_t* p
     mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
     mb.hash_leaf = lflags;
     mb.list = reinterpret_cast<uint32_t*>(llist);
-    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+    c->last_merkle_kernels = 0;
+    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
+      return AG_RS_ERR_DEVICE;
   }
   uint8_t* same = pstat;  // first validation's statuses are dead
   if (ag::launch_pipe_root_cmp(roots2, sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
@@ -3837,7 +4055,9 @@ int kind_merkle(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const u
   mb.roots = roots;
   mb.proofs = proofs;
   mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
-  return ag::launch_merkle_build(mb, c->d_merkle_nodes.as<uint8_t>(), nodes_stride, c->stream) == hipSuccess
+  c->last_merkle_kernels = 0;
+  return ag::launch_merkle_build(mb, c->d_merkle_nodes.as<uint8_t>(), nodes_stride, c->stream,
+                                 &c->last_merkle_kernels) == hipSuccess
              ? AG_RS_OK
              : AG_RS_ERR_DEVICE;
 }

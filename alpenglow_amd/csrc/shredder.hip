@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void pipe_expand_kernel(const PipeExpandParams
   const bool skip = (p.skip && ((p.skip[s] >> j) & 1)) || (p.slice_ok && !p.slice_ok[s]);
   p.kind[t] = j >= p.num_data ? 1 : 0;
   p.shred_index[t] = j;
-  p.data_len[t] = skip ? 0xFFFFFFFFu : p.shred_bytes;
+  p.data_len[t] = skip ? 0xFFFFFFFFu : p.slice_bytes ? p.slice_bytes[s] : p.shred_bytes;
   p.height[t] = kPipeHeight;
 }
 

@@ -16,7 +16,7 @@ constexpr uint32_t kPipeHeight = 6;    // Merkle path length of a 64-leaf slice 
 constexpr uint32_t kPipeNone = 0xFFu;  // no shred picked
 
 // Per-shred columns of the shred side / fill side: kind (data shreds first), shred_index,
-// data_len = S and height; rows whose skip bit is set get data_len = ~0 (the serializer then
+// data_len = S (or the slice's own size, slice_bytes) and height; rows whose skip bit is set get data_len = ~0 (the serializer then
 // leaves their packet alone).  skip: per slice, a 64-bit mask of rows to skip (nullable).
 struct PipeExpandParams {
   uint64_t nslices;
@@ -28,6 +28,7 @@ struct PipeExpandParams {
   uint32_t* shred_index;
   uint32_t* data_len;
   uint32_t* height;
+  const uint32_t* slice_bytes;  // [nslices] (nullable): slice s's data_len instead of shred_bytes
 };
 hipError_t launch_pipe_expand(const PipeExpandParams& p, hipStream_t stream);
 

@@ -178,7 +178,8 @@ __global__ __launch_bounds__(256) void shred_serialize_kernel(const ShredColumns
   const int lane = threadIdx.x & 63;
   if (t >= n) return;
   uint8_t* pk = packets + t * packet_stride;
-  const uint32_t dlen = c.data_len[t], plen = c.height[t];
+  // (row_sizes: one size per slice, wave-uniform like every other value here)
+  const uint32_t dlen = c.row_sizes ? c.row_sizes[t / kTotalShreds] : c.data_len[t], plen = c.height[t];
   const uint32_t o_sig = kShredHeadBytes + dlen;
   if (dlen > c.data_stride || 32ull * plen > c.proof_stride || uint64_t{o_sig} + 72 + 32ull * plen > packet_stride) {
     if (lane == 0) packet_lens[t] = 0;  // does not fit the caller's rows: nothing written
@@ -212,7 +213,8 @@ __global__ __launch_bounds__(256) void shred_sig_patch_kernel(const ShredColumns
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= n || packet_lens[t] == 0) return;
   const uint64_t h = c.hdr_group > 1 ? t / c.hdr_group : t;
-  uint8_t* dst = packets + t * packet_stride + kShredHeadBytes + c.data_len[t];
+  const uint32_t dlen = c.row_sizes ? c.row_sizes[t / kTotalShreds] : c.data_len[t];
+  uint8_t* dst = packets + t * packet_stride + kShredHeadBytes + dlen;
   const uint8_t* src = c.sig + 64 * h;
 #pragma unroll
   for (int q = 0; q < 4; ++q) st16u(dst + 16 * q, ld16u(src + 16 * q));

@@ -77,13 +77,14 @@ EXPORTS = (
     "ag_rs_coder_shred_batch", "ag_rs_coder_deshred_batch",
     "ag_rs_coder_shred_bytes", "ag_rs_coder_shred_batch_var", "ag_rs_coder_deshred_batch_var",
     "ag_merkle_empty_root", "ag_merkle_height", "ag_merkle_node_count", "ag_merkle_build_batch",
+    "ag_merkle_build_batch_var",
     "ag_merkle_verify_batch", "ag_block_tree_batch", "ag_block_proof_check_batch",
     "ag_aes128_encrypt_block", "ag_cipher_apply_keystream_batch", "ag_sha256_batch", "ag_aon_encrypt_batch",
     "ag_aon_decrypt_batch",
     "ag_ed25519_public_key_batch", "ag_ed25519_sign_batch", "ag_ed25519_verify_batch", "ag_shred_validate_batch",
-    "ag_slice_sign_batch", "ag_shred_deserialize_batch", "ag_shred_serialize_batch",
+    "ag_slice_sign_batch", "ag_shred_deserialize_batch", "ag_shred_serialize_batch", "ag_shred_datagram_bytes",
     "ag_slice_frame_batch", "ag_slice_parse_batch",
-    "ag_shredder_shred_batch", "ag_shredder_deshred_batch",
+    "ag_shredder_shred_batch", "ag_shredder_deshred_batch", "ag_shredder_shred_batch_var",
     "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind",
 )
 
@@ -155,6 +156,7 @@ def load():
         "ag_merkle_height": ([sz], sz),
         "ag_merkle_node_count": ([sz], sz),
         "ag_merkle_build_batch": ([p, sz, sz, sz, p, sz, sz, p, p, sz, p, sz], i),
+        "ag_merkle_build_batch_var": ([p, sz, p, p, sz, p, p, sz, p, sz], i),
         "ag_merkle_verify_batch": ([p, sz, sz, p, sz, p, p, sz, p, sz, sz, p], i),
         "ag_block_tree_batch": ([p, sz, p, p, p, p, sz, p, sz], i),
         "ag_block_proof_check_batch": ([p, sz, p, sz, p, p, sz, p, sz, p, p, p], i),
@@ -170,10 +172,12 @@ def load():
         "ag_slice_sign_batch": ([p, sz, p, p, p, p, p, p, p, p], i),
         "ag_shred_deserialize_batch": ([p, sz, p, sz, p, p, p], i),
         "ag_shred_serialize_batch": ([p, sz, p, p, sz, p], i),
+        "ag_shred_datagram_bytes": ([sz, sz, psz], i),
         "ag_slice_frame_batch": ([p, sz, sz, p, p, p, sz, p, p, sz, p], i),
         "ag_slice_parse_batch": ([p, sz, p, sz, p, p, p, p, p, p], i),
         "ag_shredder_shred_batch": ([p, sz, sz, p, p, p, sz, p, p, p, p, p, p, p, p, p, p, sz, p], i),
         "ag_shredder_deshred_batch": ([p, sz, sz, p, sz, p, p, p, p, p, p, p, p, p, p, p], i),
+        "ag_shredder_shred_batch_var": ([p, sz, p, p, p, sz, p, p, p, p, p, p, p, sz, p, p, p, p, sz, p, sz, p, p], i),
         "ag_shredder_shred_batch_kind": ([p, i, sz, sz, p, p, p, sz, p, p, p, p, p, p, p, p, sz, p, p, p, sz, p], i),
         "ag_shredder_deshred_batch_kind": ([p, i, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
     }
@@ -182,6 +186,7 @@ def load():
     sigs["ag_rs_internal_fail_next_server_job"] = ([p], i)  # test aid, not in the header
     sigs["ag_rs_internal_server_jobs"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_window_kernels"] = ([p, p], i)  # test aid, not in the header
+    sigs["ag_rs_internal_last_merkle_kernels"] = ([p, p], i)  # test aid, not in the header
     for name, (args, res) in sigs.items():
         if not hasattr(L, name):  # older build (A/B timing of a previous commit); tests
             continue              # check the shipped library exports everything
@@ -735,6 +740,29 @@ def merkle_build_batch(ctx: Context, n_leaves: int, leaf_bytes: int, nslices: in
                                         proofs_stride), "ag_merkle_build_batch")
 
 
+def merkle_build_batch_var(ctx: Context, nslices: int, leaf_bytes, leaves, slice_stride: int, roots, nodes=None,
+                           nodes_stride: int = 0, proofs=None, proofs_stride: int = 0):
+    """``merkle_build_batch`` of 64-leaf slice trees with one leaf size per slice (leaf_bytes:
+    host, one per slice): leaf j of slice s at leaves + s * slice_stride + j * leaf_bytes[s], the
+    packed codewords of ``coder_shred_batch_var``.  Outputs as ``merkle_build_batch(ctx, 64, ...)``."""
+    a = _u32(leaf_bytes, nslices)
+    _check(load().ag_merkle_build_batch_var(ctx.handle, nslices, a.ctypes.data, _optr(leaves), slice_stride,
+                                            _optr(roots), _optr(nodes), nodes_stride, _optr(proofs), proofs_stride),
+           "ag_merkle_build_batch_var")
+
+
+MERKLE_KERNELS = ("leaf_aligned", "leaf_byte", "leaf_var")
+
+
+def last_merkle_kernels(ctx: Context) -> set:
+    """The leaf-kernel classes the last Merkle build on ``ctx`` launched (test aid; the bits of
+    ``ag::MerkleLeafKernelBit``, merkle.hpp): uniform size with 16-byte-aligned rows, uniform size
+    through the byte loader, or one size per slice."""
+    out = ctypes.c_uint32(0)
+    _check(load().ag_rs_internal_last_merkle_kernels(ctx.handle, ctypes.byref(out)), "last_merkle_kernels")
+    return {name for i, name in enumerate(MERKLE_KERNELS) if out.value >> i & 1}
+
+
 def merkle_verify_batch(ctx: Context, n: int, leaf_bytes: int, leaves, leaf_stride: int, index, roots,
                         roots_stride: int, proofs, proofs_stride: int, height: int, ok):
     """check_proof for n leaves (device buffers); ok[t] = 1 / 0."""
@@ -904,6 +932,14 @@ def shred_serialize_batch(ctx: Context, n: int, cols: ShredColumns, packets, pac
                                            _ptr(packet_lens)), "ag_shred_serialize_batch")
 
 
+def shred_datagram_bytes(shred_bytes: int, proof_len: int) -> int:
+    """The encoded length of one Shred datagram with ``shred_bytes`` data bytes and a proof of
+    ``proof_len`` digests (host only); InvalidArgument above the MTU of 1500 bytes."""
+    out = ctypes.c_size_t(0)
+    _check(load().ag_shred_datagram_bytes(shred_bytes, proof_len, ctypes.byref(out)), "ag_shred_datagram_bytes")
+    return out.value
+
+
 # ---- slice payload framing (types/slice.rs:73-84, :211-218) ----------------------------
 
 SLICE_OK, SLICE_TOO_LARGE, SLICE_BAD_ENCODING, SLICE_NO_PAYLOAD = 0, 1, 2, 3
@@ -1001,6 +1037,34 @@ def shredder_shred_batch(ctx: Context, nslices: int, shred_bytes: int, parents, 
                                           _ptr(slice_indices), _ptr(is_last), _ptr(seed), _ptr(pk),
                                           _ptr(codewords), _optr(roots_out), _optr(sigs_out), _ptr(packets),
                                           packet_stride, _ptr(packet_lens)), "ag_shredder_shred_batch")
+
+
+def shredder_shred_batch_var(ctx: Context, nslices: int, parents, data, data_stride: int, data_lens, slots,
+                             slice_indices, is_last, seed, pk, codewords, codeword_stride: int, packets,
+                             packet_stride: int, packet_lens, roots_out=None, sigs_out=None, block_counts=None,
+                             block_hashes_out=None):
+    """``shredder_shred_batch`` over slices that each have their own shred size (it follows from
+    the framed payload length): slice s's 64 raw shreds are packed with its size at codewords +
+    s * codeword_stride, its datagrams go to the slots 64 s + j.  block_counts (host; slices per
+    block, summing to nslices) with block_hashes_out (device, 32 B per block): also each block's
+    hash over the slice roots.  Returns the shred sizes (numpy u32)."""
+    import numpy as np
+
+    flags, ids = _parent_arrays(parents, nslices)
+    lens = np.ascontiguousarray(np.asarray(data_lens, dtype=np.uint32))
+    if lens.size != nslices:
+        raise ValueError("data_lens do not match the batch")
+    nblocks = 0 if block_counts is None else len(block_counts)
+    counts = _u32(block_counts, nblocks) if nblocks else None
+    out = np.zeros(nslices, np.uint32)
+    _check(load().ag_shredder_shred_batch_var(ctx.handle, nslices, flags.ctypes.data, ids.ctypes.data, _optr(data),
+                                              data_stride, lens.ctypes.data, _ptr(slots), _ptr(slice_indices),
+                                              _ptr(is_last), _ptr(seed), _ptr(pk), _optr(codewords), codeword_stride,
+                                              out.ctypes.data, _optr(roots_out), _optr(sigs_out), _optr(packets),
+                                              packet_stride, _optr(packet_lens), nblocks,
+                                              counts.ctypes.data if nblocks else None, _optr(block_hashes_out)),
+           "ag_shredder_shred_batch_var")
+    return out
 
 
 @dataclass

@@ -15,6 +15,9 @@ Python hashlib / OpenSSL SHA-256, one thread, bounded sample).
 
 --block-tree times the block trees instead (ag_block_tree_batch: the double-Merkle tree over a
 block's slice roots), one JSON line per shape; see block_tree_leg.
+
+--mixed-sizes times the slice trees of a block's mix of shred sizes (bench_coder.mixed_sizes)
+through ag_merkle_build_batch_var against the uniform call; see mixed_leg.
 """
 from __future__ import annotations
 
@@ -102,6 +105,109 @@ def block_tree_leg(args):
     ctx.close()
 
 
+def mixed_leg(args):
+    """--mixed-sizes: roots + proofs of --slices slice trees, one 64 KiB codeword region per slice
+    (the var coder's packed layout), legs interleaved step by step:
+      uniform_1024   ag_merkle_build_batch at S = 1024: every row 16-byte aligned, the ceiling
+      uniform_1010   the same at S = 1010: rows 2-byte aligned, the per-byte loader
+      var_1024       ag_merkle_build_batch_var, every slice 1024: the var loader on aligned rows
+      var_1010       ag_merkle_build_batch_var, every slice 1010
+      var_mix        ag_merkle_build_batch_var on bench_coder.mixed_sizes
+      presorted_mix  the mix sorted by size, one uniform call per distinct size (the caller's
+                     gather and scatter are not timed)
+      runs_mix       the mix in block order, one uniform call per run of equal sizes -- what a
+                     caller can do without the var call (host-bound: timed over 2 steps)
+    Per leg the median over --steps of the host's wall time from the call to the end of a
+    synchronise, and of the HIP events around it.  One JSON line."""
+    import statistics
+
+    import numpy as np
+    import torch
+
+    import bench_coder
+    from alpenglow_amd import rs
+
+    dev = torch.device("cuda:0")
+    ctx = rs.Context(0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)
+    n, L, stride = args.slices, 64, 64 * 1024
+    pstride = 32 * rs.merkle_height(L) * L
+    buf = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    rs.fill_splitmix(ctx, buf, n, stride, stride, 0x3E2C1E00)
+    roots = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    proofs = torch.empty((n, pstride), dtype=torch.uint8, device=dev)
+    mix = bench_coder.mixed_sizes(n)
+    order = np.argsort(mix, kind="stable")
+    srt = mix[order]
+    starts = np.flatnonzero(np.r_[True, srt[1:] != srt[:-1]]).tolist() + [n]
+    cuts = np.flatnonzero(np.r_[True, mix[1:] != mix[:-1]]).tolist() + [n]
+    all1010, all1024 = np.full(n, 1010, np.uint32), np.full(n, 1024, np.uint32)
+
+    def uniform(S, b=0, e=n):
+        rs.merkle_build_batch(ctx, L, S, e - b, buf[b:e], S, stride, roots[b:e], None, 0, proofs[b:e], pstride)
+
+    def var(sizes):
+        rs.merkle_build_batch_var(ctx, n, sizes, buf, stride, roots, None, 0, proofs, pstride)
+
+    def per_run(sizes, edges, limit=n):
+        for b, e in zip(edges[:-1], edges[1:]):
+            if b >= limit:
+                break
+            uniform(int(sizes[b]), b, e)
+
+    legs = {"uniform_1024": lambda: uniform(1024), "uniform_1010": lambda: uniform(1010),
+            "var_1024": lambda: var(all1024), "var_1010": lambda: var(all1010), "var_mix": lambda: var(mix),
+            "presorted_mix": lambda: per_run(srt, starts)}
+
+    def timed(f):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record(stream)
+        f()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, e0.elapsed_time(e1)
+
+    # the outputs agree where the legs hash the same leaves: var_mix against runs_mix (block order)
+    var(mix)
+    want = roots.clone(), proofs.clone()
+    per_run(mix, cuts)
+    torch.cuda.synchronize()
+    same = torch.equal(roots, want[0]) and torch.equal(proofs, want[1])
+    del want
+    for _ in range(max(args.warmup, 2)):
+        for f in legs.values():
+            f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in legs}
+    for _ in range(args.steps):
+        for k, f in legs.items():
+            times[k].append(timed(f))
+    times["runs_mix"] = [timed(lambda: per_run(mix, cuts)) for _ in range(2)]
+    out = {}
+    for k, v in times.items():
+        wall, devms = statistics.median(t[0] for t in v), statistics.median(t[1] for t in v)
+        out[k] = {"wall_ms": wall, "device_ms": devms, "slices_per_s": n / (wall * 1e-3), "steps": len(v)}
+    print(json.dumps({
+        "metric": "slices/s slice Merkle trees (roots + proofs) over a block's mix of shred sizes, one var call",
+        "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "higher_is_better": True, "n_gpus": 1,
+        "steps": args.steps, "warmup": max(args.warmup, 2),
+        "config": {"slices": n, "slice_stride": stride, "distinct_sizes": len(starts) - 1, "runs": len(cuts) - 1,
+                   "mean_shred_bytes": float(mix.mean())},
+        "legs": out,
+        "ratios": {"var_1010_over_uniform_1010": out["uniform_1010"]["wall_ms"] / out["var_1010"]["wall_ms"],
+                   "var_1010_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_1010"]["wall_ms"],
+                   "var_1024_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_1024"]["wall_ms"],
+                   "var_mix_over_runs_mix": out["runs_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
+                   "var_mix_over_presorted_mix": out["presorted_mix"]["wall_ms"] / out["var_mix"]["wall_ms"]},
+        "verify": {"var_mix_equals_runs_mix": same},
+    }), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--slices", type=int, default=65536)
@@ -112,9 +218,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--block-tree", action="store_true",
                     help="time ag_block_tree_batch (block hashes over slice roots) instead of the slice trees")
+    ap.add_argument("--mixed-sizes", action="store_true",
+                    help="time ag_merkle_build_batch_var on a block's mix of shred sizes against the uniform call")
     args = ap.parse_args()
     if args.block_tree:
         return block_tree_leg(args)
+    if args.mixed_sizes:
+        return mixed_leg(args)
     import torch
 
     from alpenglow_amd import rs

@@ -14,6 +14,9 @@ slot_block_data.rs:331-370) and fills in the rest.  Device-resident buffers; wal
 around each (synchronous) call.  Prints one JSON line; the verify block checks the round
 trip (every payload and datagram restored) and a spot check against the CPU composition of
 the reference (oracle/shredder_oracle.py, checker only).
+
+--mixed-sizes times the shred side over a block's mix of shred sizes (bench_coder.mixed_sizes)
+through ag_shredder_shred_batch_var against loops of the uniform call; see mixed_leg.
 """
 from __future__ import annotations
 
@@ -33,6 +36,109 @@ NAMES = {"regular": "RegularShredder", "coding_only": "CodingOnlyShredder", "pet
 KINDS = {"regular": (0, 32, 0), "coding_only": (1, 64, 0), "pets": (2, 33, 16), "aont": (3, 32, 16)}
 
 
+def mixed_leg(args):
+    """--mixed-sizes: RegularShredder::shred of --slices slices whose shred sizes are a block's mix
+    (the longest payload of each size, no parents), legs interleaved step by step:
+      var_mix        ag_shredder_shred_batch_var, one call
+      presorted_mix  the mix sorted by size, ag_shredder_shred_batch once per distinct size (the
+                     caller's gather and scatter are not timed)
+      uniform_1024   ag_shredder_shred_batch on maximum slices (the uniform rate, beside both)
+      runs_mix       the mix in block order, ag_shredder_shred_batch once per run of equal sizes --
+                     what a caller can do without the var call (host-bound: timed once)
+    Per leg the median over --steps of the host's wall time from the call to the end of a
+    synchronise.  One JSON line; the verify block compares var_mix's datagrams, lengths and roots
+    with runs_mix's."""
+    import statistics
+
+    import numpy as np
+    import torch
+
+    import bench_coder
+    from alpenglow_amd import rs
+
+    dev = torch.device("cuda:0")
+    torch.zeros(1, device=dev)
+    ctx = rs.Context(0)
+    stream = torch.cuda.Stream(dev)
+    torch.cuda.set_stream(stream)
+    ctx.set_stream(stream.cuda_stream)
+    n, stride = args.slices, 64 * 1024
+    mix = bench_coder.mixed_sizes(n)
+    dmix = (32 * mix.astype(np.int64) - 1 - 9).astype(np.uint32)  # data bytes: framed payload 32 S - 1
+    data = torch.empty((n, 32 * 1024), dtype=torch.uint8, device=dev)
+    rs.fill_splitmix(ctx, data, n, 32 * 1024, 32 * 1024, 0x5EED0000)
+    g = torch.Generator(device="cpu").manual_seed(0xA221)
+    slots = torch.randint(0, 1 << 40, (n,), generator=g, dtype=torch.int64).to(dev)
+    sidx = torch.randint(0, 1024, (n,), generator=g, dtype=torch.int64).to(dev)
+    last = (torch.arange(n) % 1024 == 1023).to(torch.uint8).to(dev)
+    seed = torch.arange(32, dtype=torch.uint8).to(dev)
+    pk = torch.empty(32, dtype=torch.uint8, device=dev)
+    rs.ed25519_public_key_batch(ctx, 1, seed, pk)
+    cw = torch.zeros(n * stride, dtype=torch.uint8, device=dev)
+    pkts = torch.zeros((n * 64, PKT), dtype=torch.uint8, device=dev)
+    lens = torch.zeros(n * 64, dtype=torch.int32, device=dev)
+    roots = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+    parents = [None] * n
+    order = np.argsort(mix, kind="stable")
+    srt, dsrt = mix[order], dmix[order]
+    starts = np.flatnonzero(np.r_[True, srt[1:] != srt[:-1]]).tolist() + [n]
+    cuts = np.flatnonzero(np.r_[True, mix[1:] != mix[:-1]]).tolist() + [n]
+    d1024 = np.full(n, 32 * 1024 - 1 - 9, np.uint32)
+
+    def var():
+        rs.shredder_shred_batch_var(ctx, n, parents, data, 32 * 1024, dmix, slots, sidx, last, seed, pk, cw, stride,
+                                    pkts, PKT, lens, roots_out=roots)
+
+    def uniform(S, dl, b=0, e=n):
+        rs.shredder_shred_batch(ctx, e - b, S, parents[b:e], data[b:e], 32 * 1024, dl[b:e], slots[b:e], sidx[b:e],
+                                last[b:e], seed, pk, cw.data_ptr() + b * stride, pkts[64 * b:64 * e], PKT,
+                                lens[64 * b:64 * e], roots_out=roots[b:e])
+
+    def per_run(sizes, dl, edges):
+        for b, e in zip(edges[:-1], edges[1:]):
+            uniform(int(sizes[b]), dl, b, e)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        f()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    var()
+    torch.cuda.synchronize()
+    want = pkts.clone(), lens.clone(), roots.clone()
+    pkts.zero_()
+    t_runs = timed(lambda: per_run(mix, dmix, cuts))
+    same = torch.equal(pkts, want[0]) and torch.equal(lens, want[1]) and torch.equal(roots, want[2])
+    del want
+    legs = {"var_mix": var, "presorted_mix": lambda: per_run(srt, dsrt, starts),
+            "uniform_1024": lambda: uniform(1024, d1024)}
+    for _ in range(max(args.warmup, 2)):
+        for f in legs.values():
+            f()
+    times = {k: [] for k in legs}
+    for _ in range(args.steps):
+        for k, f in legs.items():
+            times[k].append(timed(f))
+    times["runs_mix"] = [t_runs]
+    out = {k: {"wall_ms": statistics.median(v), "slices_per_s": n / (statistics.median(v) * 1e-3), "steps": len(v)}
+           for k, v in times.items()}
+    print(json.dumps({
+        "metric": "slices/s composed RegularShredder shred over a block's mix of shred sizes, one var call",
+        "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "higher_is_better": True, "n_gpus": 1,
+        "steps": args.steps, "warmup": max(args.warmup, 2),
+        "config": {"slices": n, "codeword_stride": stride, "packet_stride": PKT, "distinct_sizes": len(starts) - 1,
+                   "runs": len(cuts) - 1, "mean_shred_bytes": float(mix.mean())},
+        "legs": out,
+        "ratios": {"var_mix_over_runs_mix": out["runs_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
+                   "var_mix_over_presorted_mix": out["presorted_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
+                   "var_mix_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_mix"]["wall_ms"]},
+        "verify": {"var_mix_equals_runs_mix": same},
+    }), flush=True)
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--slices", type=int, default=65536)
@@ -44,7 +150,11 @@ def main():
                     help="shred size S (even, <= 1024): payloads of 32 S - 1 bytes; 1024 = maximum slices")
     ap.add_argument("--kind", choices=list(KINDS), default="regular",
                     help="the shredder (shredder.rs:336-500); the CPU baseline is timed for regular only")
+    ap.add_argument("--mixed-sizes", action="store_true",
+                    help="time ag_shredder_shred_batch_var on a block's mix of shred sizes against the uniform call")
     args = ap.parse_args()
+    if args.mixed_sizes:
+        return mixed_leg(args)
     import numpy as np
     import torch
 

@@ -339,6 +339,20 @@ size_t ag_merkle_node_count(size_t n_leaves);
 int ag_merkle_build_batch(ag_rs_ctx* ctx, size_t n_leaves, size_t leaf_bytes, size_t nslices,
                           const uint8_t* leaves, size_t leaf_stride, size_t slice_stride, uint8_t* roots,
                           uint8_t* nodes, size_t nodes_stride, uint8_t* proofs, size_t proofs_stride);
+/* build_batch_var: the slice trees (64 leaves each, TOTAL_SHREDS) of slices of mixed shred
+ * sizes in one call.  leaf_bytes (HOST, nslices) gives slice s's leaf size S_s (even, 2 ..
+ * 1024); leaf j of slice s is S_s bytes at leaves + s*slice_stride + j*S_s -- the packed
+ * codewords of ag_rs_coder_shred_batch_var.  roots, nodes, proofs: exactly the bytes and
+ * layouts of ag_merkle_build_batch(ctx, 64, S_s, 1, ...) on each slice alone.  The number of
+ * launches does not depend on the mix of sizes.  Asynchronous on the context stream
+ * (leaf_bytes is copied before the call returns).
+ * Whole-call errors (nothing launched, outputs untouched): INVALID_SHARD_SIZE (an S_s of zero
+ * or odd), TOO_MUCH_DATA (an S_s > 1024), INVALID_ARGUMENT (slice_stride < 64 * max S_s, a
+ * null ctx / leaf_bytes / leaves / roots with nslices > 0, nodes_stride or proofs_stride too
+ * small or no multiple of 16, roots / nodes / proofs not 16-byte aligned, nslices > 2^27). */
+int ag_merkle_build_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint32_t* leaf_bytes,
+                              const uint8_t* leaves, size_t slice_stride, uint8_t* roots, uint8_t* nodes,
+                              size_t nodes_stride, uint8_t* proofs, size_t proofs_stride);
 /* check_proof (merkle.rs:374-387) for n leaves: leaf t at leaves + t*leaf_stride, index[t],
  * root at roots + t*roots_stride, height digests at proofs + t*proofs_stride;
  * ok[t] = 1 if the proof derives the root, else 0. */
@@ -482,6 +496,11 @@ int ag_shred_deserialize_batch(ag_rs_ctx* ctx, size_t n, const uint8_t* packets,
  * shred does not fit packet_stride or its own rows. */
 int ag_shred_serialize_batch(ag_rs_ctx* ctx, size_t n, const ag_shred_columns* cols, uint8_t* packets,
                              size_t packet_stride, uint32_t* packet_lens);
+/* The encoded length of one Shred datagram carrying shred_bytes data bytes and proof_len
+ * digests: 37 + shred_bytes + 64 + 8 + 32 * proof_len (1325 for a 1 KiB shred of a slice
+ * tree, proof_len = 6).  Host only, needs no device.  INVALID_ARGUMENT when the datagram
+ * exceeds the MTU (1500 bytes, network.rs:45) or out is NULL. */
+int ag_shred_datagram_bytes(size_t shred_bytes, size_t proof_len, size_t* out);
 
 /* ---- 9. composed Shredder (RegularShredder, 32 data + 32 coding shreds) ----------------
  * One call per direction for nslices slices of one shred size S (even, <= 1024), every
@@ -525,6 +544,32 @@ int ag_shredder_deshred_batch(ag_rs_ctx* ctx, size_t nslices, size_t shred_bytes
                               int32_t* status, uint64_t* slots_out, uint64_t* slice_indices_out,
                               uint8_t* is_last_out, uint8_t* parent_flags_out, uint8_t* parent_ids_out,
                               uint32_t* data_offsets_out, uint32_t* data_lens_out);
+
+/* shred_batch_var -- RegularShredder::shred over slices that each have their own shred size
+ * (a block's slices: full ones close at 1008 .. 1024, a timed-out one at any even size;
+ * block_producer.rs:453-474), in a fixed number of launches whatever the mix.  Slice s's
+ * size S_s follows from its framed payload length (ag_rs_coder_shred_bytes) and is returned
+ * in shred_bytes_out (HOST, nslices, nullable).  Its 64 raw shreds are packed with stride S_s
+ * at codewords + s * codeword_stride (16-byte aligned, codeword_stride % 16 == 0; no byte past
+ * 64 * S_s of a slice's stride is written), its 64 datagrams go to the slots packets + (64 s +
+ * j) * packet_stride, written exactly (no byte of a slot past packet_lens is touched).  The
+ * other arguments and every output byte are those of ag_shredder_shred_batch run on each
+ * slice alone at S = S_s.
+ * nblocks > 0: consecutive groups of block_counts[b] (HOST; 1 .. 1024, summing to nslices)
+ * slices are blocks, and block_hashes_out (device, 32 B per block, 16-byte aligned) receives
+ * each block's ag_block_tree_batch hash over the slice roots just computed; nblocks = 0 skips
+ * it (block_counts / block_hashes_out unused).
+ * Errors (nothing launched, nothing written): TOO_MUCH_DATA (a framed slice above 32767
+ * bytes), INVALID_ARGUMENT (codeword_stride < 64 * max S_s, codewords or codeword_stride no
+ * multiple of 16, packet_stride < ag_shred_datagram_bytes(max S_s, 6), block counts that are
+ * zero, above 1024 or do not sum to nslices, a null pointer, nslices >= 2^24). */
+int ag_shredder_shred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint8_t* parent_flags,
+                                const uint8_t* parent_ids, const uint8_t* data, size_t data_stride,
+                                const uint32_t* data_lens, const uint64_t* slots, const uint64_t* slice_indices,
+                                const uint8_t* is_last, const uint8_t* seed, const uint8_t* pk, uint8_t* codewords,
+                                size_t codeword_stride, uint32_t* shred_bytes_out, uint8_t* roots_out,
+                                uint8_t* sigs_out, uint8_t* packets, size_t packet_stride, uint32_t* packet_lens,
+                                size_t nblocks, const uint32_t* block_counts, uint8_t* block_hashes_out);
 
 /* The other shredders of shredder.rs, composed the same way (round 6):
  *   AG_SHREDDER_CODING_ONLY  CodingOnlyShredder (:361-394): ReedSolomonCoder::new(64), the 64
