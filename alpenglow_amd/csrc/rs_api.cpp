@@ -28,10 +28,12 @@
 #include "slice.hpp"
 #include "wire.hpp"
 #include "merkle.hpp"
+#include "rs_ctx.hpp"
 #include "rs_launch.hpp"
 #include "rs_patterns.hpp"
 #include "shredder.hpp"
 
+using namespace ag::host;  // the context's buffers and the helpers shared with shredder_api.cpp
 using ag::build_corr_pattern;
 using ag::build_syn_pattern;
 using ag::corr_fits;
@@ -43,74 +45,6 @@ using ag::window128_masks;
 using ag::window64_masks;
 
 namespace {
-
-#define AG_HIP(expr)                                  \
-  do {                                                \
-    if ((expr) != hipSuccess) return AG_RS_ERR_DEVICE; \
-  } while (0)
-
-// Grow-only device buffer.
-struct DevBuf {
-  void* ptr = nullptr;
-  size_t size = 0;
-  int ensure(size_t n, hipStream_t stream) {
-    if (n <= size) return AG_RS_OK;
-    if (ptr) {
-      if (hipStreamSynchronize(stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-      (void)hipFree(ptr);
-      ptr = nullptr;
-      size = 0;
-    }
-    if (hipMalloc(&ptr, n) != hipSuccess) return AG_RS_ERR_OUT_OF_MEMORY;
-    size = n;
-    return AG_RS_OK;
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(ptr);
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    size = 0;
-  }
-};
-
-// Grow-only pinned host buffer, mapped and coherent (fine-grained: never cached in the GPU's
-// L2, so one call's kernels cannot read another call's stale bytes): the crate-API
-// single-call kernels read and write it directly (zero-copy).
-struct PinBuf {
-  void* ptr = nullptr;
-  size_t size = 0;
-  int ensure(size_t n) {
-    if (n <= size) return AG_RS_OK;
-    release();
-    if (hipHostMalloc(&ptr, n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-      ptr = nullptr;
-      return AG_RS_ERR_OUT_OF_MEMORY;
-    }
-    if (hipHostGetDevicePointer(&dptr, ptr, 0) != hipSuccess) {
-      release();
-      return AG_RS_ERR_DEVICE;
-    }
-    size = n;
-    return AG_RS_OK;
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(ptr);
-  }
-  template <typename T>
-  T* dev() const {  // the same bytes as the device addresses them (zero-copy over PCIe)
-    return static_cast<T*>(dptr);
-  }
-  void* dptr = nullptr;
-  void release() {
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = dptr = nullptr;
-    size = 0;
-  }
-};
 
 int check_geometry(size_t k, size_t m, size_t S) {
   if (ag::use_high_rate(k, m) < 0) return AG_RS_ERR_UNSUPPORTED_SHARD_COUNT;
@@ -147,224 +81,6 @@ unsigned lowrate_chunk(size_t k, size_t m, size_t S) {
   if (c == 64 && chunks <= 3) return 64;
   return 0;
 }
-
-}  // namespace
-
-struct ag_rs_ctx {
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  bool tables_ready = false;
-  DevBuf d_exp, d_log, d_skew, d_log_walsh;
-  DevBuf scratch;                         // generic-kernel work rows
-  DevBuf d_flags, d_loc, d_blocks, d_mask;  // decode bookkeeping
-  DevBuf d_xmask, d_rows, d_xblocks;        // bitsliced general decode: masks, matrices
-  DevBuf d_x128, d_rows128;                 // W = 128 two-pass decode: masks, constants
-  uint64_t last_classes[16] = {};           // patterns per decoder class of the last decode call
-  int decode_depth = 0;                     // decode_device nesting (tail restrides decode inside)
-  uint32_t last_encode_kernels = 0;         // EncodeKernelBit of the last ag_rs_encode_batch / coder deshred batch
-  uint32_t last_window_kernels = 0;         // DecodeXKernelBit of the last coder deshred batch's window decode
-  DevBuf d_syn, d_synblocks;                // syndrome decoder: patterns, block ids
-  DevBuf d_corr, d_corrk, d_corrblocks;     // correction decoder: patterns, K picks, block ids
-  DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
-  DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
-  uint32_t last_merkle_kernels = 0;         // MerkleLeafKernelBit of the last Merkle build's leaf kernel
-  DevBuf d_leaf_sizes;                      // ag_merkle_build_batch_var: leaf size per slice
-  PinBuf h_leaf_sizes;                      // its pinned host staging
-  hipEvent_t leaf_sizes_ev = nullptr;       // recorded after its upload
-  DevBuf d_block_meta;                      // block trees: first[nblocks] (u64), then count[nblocks] (u32)
-  PinBuf h_block_meta;                      // its pinned host staging
-  hipEvent_t block_meta_ev = nullptr;       // recorded after its upload
-  DevBuf d_aon_lens, d_aon_digests, d_aon_keys;  // all-or-nothing transforms
-  DevBuf d_aon_lens2;                            // the side stream's SHA-256 lengths (AONT deshred)
-  hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
-  hipEvent_t side_fork = nullptr, side_join = nullptr;
-  DevBuf d_slice_meta;                           // slice framing / parsing metadata
-  DevBuf stage_pad, stage_mask;                  // restrided shards (sizes not whole 64-byte chunks)
-  DevBuf d_lens, d_strip;                   // coder batches: payload lengths, strip results
-  DevBuf d_reenc_mask;                      // uniform coder deshreds: the re-encode's store mask word
-  DevBuf d_pipe_few, d_pipe_mask;           // composed deshred: too-few flags, re-encode store masks
-  DevBuf d_present;                         // coder batches: per-slice present masks
-  PinBuf h_present;                         // their pinned host staging
-  hipEvent_t present_ev = nullptr;          // recorded after its upload
-  PinBuf h_lens;                            // coder shred batches: pinned staging of the lengths
-  hipEvent_t lens_ev = nullptr;             // recorded after its upload
-  PinBuf h_strip;                           // coder deshred batches: pinned staging of the results
-  PinBuf h_slice_meta;                      // slice parse batches: pinned staging of the results
-  PinBuf h_pipe_meta;                       // composed deshreds: pinned staging of the per-slice columns
-  DevBuf d_ed_base;                         // Ed25519 fixed-base table (ed25519.hpp)
-  static constexpr int kPipeBufs = 28;
-  DevBuf pipe[kPipeBufs];                   // composed shredder scratch (ag_shredder_*_batch)
-  DevBuf d_sh_roots, d_sh_commit, d_sh_onvalid, d_sh_list;  // shred validation scratch
-  DevBuf stage_in, stage_out;             // host-memory calls (unused; see slots)
-  // host-memory calls: two staging slots, H2D / D2H streams next to the compute stream
-  struct Slot {
-    DevBuf in, out;
-    hipEvent_t up = nullptr, done = nullptr, down = nullptr;
-  } slot[2];
-  hipStream_t h2d = nullptr, d2h = nullptr;
-  DevBuf one_in, one_out;                 // crate-API single codeword
-  // per-call server (latency_server_kernel): mailbox in mapped host memory, its own stream
-  ag::LatencyMailbox* mb = nullptr;
-  ag::LatencyMailbox* mb_dev = nullptr;
-  hipStream_t server_stream = nullptr;
-  uint32_t server_seq = 0;
-  uint32_t server_p_seq = 0, server_dp_seq = 0;  // versions of the parameters last posted
-  bool server_broken = false;  // a job timed out: the server path is off for this context
-  bool fail_next_server_job = false;  // test aid: the next server job takes the timeout path
-  uint64_t server_jobs[4] = {};        // jobs posted per LatencyJob kind (test aid)
-  std::vector<PinBuf> abandoned_pins;  // staging a timed-out job named (freed once the server is gone)
-  std::vector<uint64_t> mask_host;        // last store-mask words uploaded to d_mask
-  std::vector<uint64_t> stage_mask_host;  // last restride masks uploaded to stage_mask
-  std::vector<uint64_t> xmask_host;       // last general-decode masks (d_xmask), W = xmask_w
-  size_t xmask_w = 0;
-  bool xmask_poly = false;                // d_rows holds polynomial-basis constants (per-lane)
-  std::vector<uint8_t> syn_key;             // (k, m, present flags) of the patterns in d_syn
-  std::vector<uint8_t> corr_key;            // (k, m, present flags) of the patterns in d_corr
-  std::vector<uint64_t> x128_host;          // last W = 128 masks uploaded to d_x128
-  std::vector<uint32_t> x128_ids;           // their per-block ids (d_xblocks)
-
-  int enter() { return hipSetDevice(device) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE; }
-
-  int ensure_tables() {
-    if (tables_ready) return AG_RS_OK;
-    const ag::Gf16Tables& t = ag::gf16_tables();
-    // log_walsh: Walsh-Hadamard transform (mod 65535) of the log table with log[0] := 0
-    // (crate engine/tables.rs initialize_log_walsh).
-    std::vector<uint16_t> lw(t.log, t.log + ag::kGfOrder);
-    lw[0] = 0;
-    for (size_t dist = 1; dist < ag::kGfOrder; dist <<= 1)
-      for (size_t r = 0; r < ag::kGfOrder; r += 2 * dist)
-        for (size_t i = r; i < r + dist; ++i) {
-          const uint32_t a = lw[i], b = lw[i + dist];
-          const uint32_t s = a + b, d = a - b;
-          lw[i] = static_cast<uint16_t>(s + (s >> 16));
-          lw[i + dist] = static_cast<uint16_t>(d + (d >> 16));
-        }
-    int st;
-    if ((st = d_exp.ensure(sizeof t.exp, stream)) || (st = d_log.ensure(sizeof t.log, stream)) ||
-        (st = d_skew.ensure(sizeof t.skew, stream)) || (st = d_log_walsh.ensure(lw.size() * 2, stream)))
-      return st;
-    AG_HIP(hipMemcpy(d_exp.ptr, t.exp, sizeof t.exp, hipMemcpyHostToDevice));
-    AG_HIP(hipMemcpy(d_log.ptr, t.log, sizeof t.log, hipMemcpyHostToDevice));
-    AG_HIP(hipMemcpy(d_skew.ptr, t.skew, sizeof t.skew, hipMemcpyHostToDevice));
-    AG_HIP(hipMemcpy(d_log_walsh.ptr, lw.data(), lw.size() * 2, hipMemcpyHostToDevice));
-    tables_ready = true;
-    return AG_RS_OK;
-  }
-
-  ag::GfDeviceTables dtables() const {
-    return {d_exp.as<uint16_t>(), d_log.as<uint16_t>(), d_skew.as<uint16_t>(), d_log_walsh.as<uint16_t>()};
-  }
-
-  int ensure_side_stream() {
-    if (side) return AG_RS_OK;
-    AG_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-    AG_HIP(hipEventCreateWithFlags(&side_fork, hipEventDisableTiming));
-    AG_HIP(hipEventCreateWithFlags(&side_join, hipEventDisableTiming));
-    return AG_RS_OK;
-  }
-
-  int ensure_copy_streams() {
-    if (h2d) return AG_RS_OK;
-    AG_HIP(hipStreamCreateWithFlags(&h2d, hipStreamNonBlocking));
-    AG_HIP(hipStreamCreateWithFlags(&d2h, hipStreamNonBlocking));
-    for (Slot& s : slot) {
-      AG_HIP(hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
-      AG_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-      AG_HIP(hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
-      AG_HIP(hipEventRecord(s.down, d2h));  // slots start free
-    }
-    return AG_RS_OK;
-  }
-
-  void server_stop() {
-    if (!mb) return;
-    (void)hipSetDevice(device);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0) {
-      mb->kind = ag::kJobQuit;
-      __atomic_store_n(&mb->doorbell, ++server_seq, __ATOMIC_RELEASE);
-      while (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0 &&
-             std::chrono::steady_clock::now() - t0 < std::chrono::seconds(2)) {
-      }
-    }
-    if (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0) {
-      // a server that neither served nor quit (server_broken): waiting on its stream could
-      // block forever, and it may still write the mailbox or an abandoned staging buffer,
-      // so those stay allocated
-      mb = mb_dev = nullptr;
-      server_stream = nullptr;
-      abandoned_pins.clear();
-      return;
-    }
-    (void)hipStreamSynchronize(server_stream);  // the server has exited (quit or idle timeout)
-    for (PinBuf& b : abandoned_pins) b.release();
-    abandoned_pins.clear();
-    (void)hipStreamDestroy(server_stream);
-    (void)hipHostFree(mb);
-    mb = mb_dev = nullptr;
-    server_stream = nullptr;
-  }
-
-  ~ag_rs_ctx() {
-    server_stop();
-    if (side) {
-      (void)hipSetDevice(device);
-      (void)hipStreamSynchronize(side);
-      (void)hipEventDestroy(side_fork);
-      (void)hipEventDestroy(side_join);
-      (void)hipStreamDestroy(side);
-    }
-    if (own_stream) {
-      (void)hipSetDevice(device);
-      (void)hipStreamSynchronize(own_stream);
-    }
-    if (h2d) {
-      (void)hipStreamSynchronize(h2d);
-      (void)hipStreamSynchronize(d2h);
-      for (Slot& s : slot) {
-        s.in.release();
-        s.out.release();
-        for (hipEvent_t e : {s.up, s.done, s.down})
-          if (e) (void)hipEventDestroy(e);
-      }
-      (void)hipStreamDestroy(h2d);
-      (void)hipStreamDestroy(d2h);
-    }
-    for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &d_mask,
-                      &d_xmask, &d_rows, &d_xblocks, &d_x128, &d_rows128, &d_syn, &d_synblocks, &d_corr, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_in, &stage_out, &stage_pad, &stage_mask, &d_slice_meta, &one_in,
-                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta, &d_leaf_sizes})
-      b->release();
-    for (DevBuf& b : pipe) b.release();
-    if (present_ev) {
-      (void)hipEventSynchronize(present_ev);
-      (void)hipEventDestroy(present_ev);
-    }
-    h_present.release();
-    if (lens_ev) {
-      (void)hipEventSynchronize(lens_ev);
-      (void)hipEventDestroy(lens_ev);
-    }
-    h_lens.release();
-    if (block_meta_ev) {
-      (void)hipEventSynchronize(block_meta_ev);
-      (void)hipEventDestroy(block_meta_ev);
-    }
-    h_block_meta.release();
-    if (leaf_sizes_ev) {
-      (void)hipEventSynchronize(leaf_sizes_ev);
-      (void)hipEventDestroy(leaf_sizes_ev);
-    }
-    h_leaf_sizes.release();
-    h_strip.release();
-    h_slice_meta.release();
-    h_pipe_meta.release();
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
-};
-
-namespace {
 
 // Host-memory calls: bytes (in + out) per staging group; two groups in flight.
 constexpr size_t kStageGroupBytes = size_t{64} << 20;
@@ -1618,7 +1334,9 @@ int ag_merkle_empty_root(size_t height, uint8_t out[32]) {
   return AG_RS_OK;
 }
 
-namespace {
+}  // extern "C"
+
+namespace ag::host {
 int ensure_empty_roots(ag_rs_ctx* c) {
   if (c->d_empty_roots.ptr) return AG_RS_OK;
   uint32_t er[ag::kMerkleMaxHeight][8];
@@ -1628,7 +1346,9 @@ int ensure_empty_roots(ag_rs_ctx* c) {
   AG_HIP(hipMemcpy(c->d_empty_roots.ptr, er, sizeof er, hipMemcpyHostToDevice));
   return AG_RS_OK;
 }
-}  // namespace
+}  // namespace ag::host
+
+extern "C" {
 
 int ag_merkle_build_batch(ag_rs_ctx* c, size_t n_leaves, size_t leaf_bytes, size_t nslices, const uint8_t* leaves,
                           size_t leaf_stride, size_t slice_stride, uint8_t* roots, uint8_t* nodes,
@@ -1693,7 +1413,10 @@ int merkle_var_check(size_t nslices, const uint32_t* leaf_bytes, const uint8_t* 
     return AG_RS_ERR_INVALID_ARGUMENT;
   return AG_RS_OK;
 }
+}  // namespace
+}  // extern "C"
 
+namespace ag::host {
 // The launches of ag_merkle_build_batch_var over sizes already on the device (d_sizes; checked by
 // the caller on the host): the composed shred hands over the table its coder stage uploaded.
 int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
@@ -1721,7 +1444,9 @@ int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, con
              ? AG_RS_OK
              : AG_RS_ERR_DEVICE;
 }
-}  // namespace
+}  // namespace ag::host
+
+extern "C" {
 
 int ag_merkle_build_batch_var(ag_rs_ctx* c, size_t nslices, const uint32_t* leaf_bytes, const uint8_t* leaves,
                               size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride,
@@ -1864,7 +1589,9 @@ int ag_aes128_encrypt_block(const uint8_t key[16], const uint8_t in[16], uint8_t
   return AG_RS_OK;
 }
 
-namespace {
+}  // extern "C"
+
+namespace ag::host {
 // lengths (host) -> device; the batch descriptor
 int aon_batch(ag_rs_ctx* c, size_t n, uint8_t* buffers, size_t stride, const uint32_t* lens, uint32_t extra,
               ag::BufferBatch* bb) {
@@ -1885,7 +1612,9 @@ int aon_batch(ag_rs_ctx* c, size_t n, uint8_t* buffers, size_t stride, const uin
   bb->max_len = mx;
   return AG_RS_OK;
 }
-}  // namespace
+}  // namespace ag::host
+
+extern "C" {
 
 int ag_cipher_apply_keystream_batch(ag_rs_ctx* c, size_t n, const uint8_t* keys, uint8_t* buffers, size_t stride,
                                     const uint32_t* lens) {
@@ -2459,10 +2188,9 @@ int ag_rs_internal_coder_last_job_ns(ag_rs_coder* coder, uint64_t* ns) {
 }
 
 namespace {
-constexpr size_t kDataShreds = AG_RS_DATA_SHREDS;
 constexpr size_t kTotalShreds = AG_RS_TOTAL_SHREDS;
 constexpr size_t kMaxAfterPadding = kDataShreds * AG_RS_MAX_DATA_PER_SHRED;
-constexpr size_t kMaxPayload = kMaxAfterPadding - 1;
+static_assert(kMaxPayload == kMaxAfterPadding - 1);
 
 // encode_coding_from_data (reed_solomon.rs:211-231) of the 32 data shards already staged in
 // the encoder's originals (S bytes each): the coding shards land in c->enc->rec()
@@ -2628,19 +2356,6 @@ int ag_rs_coder_shred_batch(ag_rs_ctx* c, size_t m, size_t n, size_t S, const ui
     return AG_RS_ERR_DEVICE;
   return encode_device(c, kDataShreds, m, S, n, cw, cw_stride, cw + kDataShreds * S, cw_stride);
 }
-
-namespace {
-int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
-                       int64_t* plen, size_t m, bool no_surplus = false);
-// shred sizes pipe_coder_deshred decodes on the device: whole 64-byte chunks (any m of the
-// device-pattern path), or for 32:32 a last chunk of T = S mod 64 bytes -- T >= 16 always, a
-// shorter T when no slice needs the re-encode (no_reencode: no surplus shreds, no slice with
-// every data shred; the TAIL encode takes T >= 16 only)
-bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false) {
-  const size_t T = S % 64;
-  return T == 0 || (m == kDataShreds && S % 2 == 0 && (T >= 16 || no_reencode));
-}
-}  // namespace
 
 namespace {
 // Per-slice present words of ag_rs_coder_deshred_batch's device-pattern path: word 0 = data
@@ -2877,14 +2592,6 @@ int ensure_ed_base(ag_rs_ctx* c) {
   return ag::launch_ed25519_init(c->d_ed_base.as<int32_t>(), c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
 constexpr size_t kMaxSigBatch = size_t{1} << 31;
-int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data_stride, size_t data_bytes,
-                        const uint32_t* shred_index, const uint8_t* proofs, size_t proofs_stride, size_t height,
-                        const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
-                        const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
-                        const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
-                        uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes = nullptr,
-                        size_t leaf_nodes_stride = 0, uint32_t leaves_per_tree = 0, size_t group_stride = 0,
-                        uint32_t skip_row = 0, bool roots_ready = false);
 }  // namespace
 
 int ag_ed25519_public_key_batch(ag_rs_ctx* c, size_t n, const uint8_t* seeds, uint8_t* pks) {
@@ -2958,7 +2665,7 @@ int ag_shred_validate_batch(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t 
 
 }  // extern "C"
 
-namespace {
+namespace ag::host {
 
 // ag_shred_validate_batch with the cache entries shared by cached_group consecutive shreds
 // (the composed deshred: one cached commitment per slice).
@@ -3051,7 +2758,7 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
   return ag::launch_ed25519_verify(vp, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
 
-}  // namespace
+}  // namespace ag::host
 
 extern "C" {
 
@@ -3252,48 +2959,6 @@ int ag_slice_parse_batch(ag_rs_ctx* c, size_t nslices, const uint8_t* codewords,
 
 }  // extern "C"
 
-// =====================================================================================
-// Composed Shredder (RegularShredder): ag_shredder_shred_batch / ag_shredder_deshred_batch
-// =====================================================================================
-namespace {
-
-constexpr size_t kPipeProofBytes = 32 * ag::kPipeHeight;  // one Merkle path of a slice tree
-
-int pipe_buf(ag_rs_ctx* c, int i, size_t bytes, uint8_t** out) {
-  const int st = c->pipe[i].ensure(std::max<size_t>(bytes, 64), c->stream);
-  if (st) return st;
-  *out = c->pipe[i].as<uint8_t>();
-  return AG_RS_OK;
-}
-
-// The per-slice columns pipe_check writes (present | slot | slice index | is_last, contiguous
-// from `present`) read back in one copy into pinned staging: views valid until the next call
-// on the context
-struct PipeMeta {
-  const uint64_t *present, *slot, *sidx;
-  const uint8_t* last;
-};
-int read_pipe_meta(ag_rs_ctx* c, const uint64_t* d_present, size_t n, PipeMeta* m) {
-  const int st = c->h_pipe_meta.ensure(25 * n);
-  if (st) return st;
-  uint8_t* h = c->h_pipe_meta.as<uint8_t>();
-  AG_HIP(hipMemcpyAsync(h, d_present, 25 * n, hipMemcpyDeviceToHost, c->stream));
-  AG_HIP(hipStreamSynchronize(c->stream));
-  m->present = reinterpret_cast<const uint64_t*>(h);
-  m->slot = m->present + n;
-  m->sidx = m->slot + n;
-  m->last = h + 24 * n;
-  return AG_RS_OK;
-}
-
-bool pipe_args_ok(size_t nslices, size_t S, const uint8_t* codewords, const uint8_t* packets,
-                  const uint32_t* packet_lens) {
-  return S != 0 && S % 2 == 0 && S <= 1024 && nslices < (size_t{1} << 24) &&
-         (nslices == 0 || (codewords && packets && packet_lens)) && reinterpret_cast<uintptr_t>(codewords) % 16 == 0;
-}
-
-}  // namespace
-
 namespace {
 // ReedSolomonCoder::deshred (reed_solomon.rs:140-208, ANY_K) over the kept shreds of every
 // slice without a host round trip, for whole-chunk shreds (S % 64 == 0): the per-slice
@@ -3319,19 +2984,6 @@ int pipe_coder_reserve(ag_rs_ctx* c, size_t ntot, size_t m) {
   c->xmask_host.clear();  // d_xmask / d_rows no longer hold decode_device's cached patterns
   c->xmask_w = 0;
   return AG_RS_OK;
-}
-int pipe_coder_finish(ag_rs_ctx* c, size_t n, int64_t* plen);
-int pipe_coder_enqueue(ag_rs_ctx* c, size_t s0, size_t n, size_t S, uint8_t* cw, size_t cw_stride,
-                       const uint64_t* d_present, size_t m, bool no_surplus);
-// The whole batch in one range (the composed deshred's coder stage).  no_surplus: the caller
-// knows that no slice keeps more than 32 shreds and none keeps all 32 data shreds.
-int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
-                       int64_t* plen, size_t m, bool no_surplus) {
-  int st;
-  if ((st = pipe_coder_reserve(c, n, m)) ||
-      (st = pipe_coder_enqueue(c, 0, n, S, cw, cw_stride, d_present, m, no_surplus)))
-    return st;
-  return pipe_coder_finish(c, n, plen);
 }
 // The same for CodingOnlyShredder's coder (LowRate 32:64, shredder.rs:362-395) and
 // PetsShredder's (32:33, :403-444; its recovery shards are the first 33 of 32:64's): every slice
@@ -3479,1020 +3131,30 @@ int pipe_coder_finish(ag_rs_ctx* c, size_t n, int64_t* plen) {
   std::memcpy(plen, c->h_strip.ptr, 8 * n);
   return AG_RS_OK;
 }
-// Step 6b of ag_shredder_deshred_batch for slice s: its datagram rows are parsed again into
-// the codeword (the pass before rewrote the restored and re-encoded rows), the kept shreds
-// (present bit mask) go through ReedSolomonCoder::deshred with the crate's EXACT decoder,
-// and the Merkle rebuild (roots2 row s, the slice's proof rows), root comparison and
-// SlicePayload parse are redone for this slice.  Outputs replace slice s's entries.
-int pipe_rerun_exact(ag_rs_ctx* c, size_t s, size_t S, const uint8_t* packets, size_t packet_stride,
-                     const uint32_t* packet_lens, const ag::ShredColumns& cols, uint8_t* wire, uint8_t* codewords,
-                     uint8_t* proof, uint8_t* roots2, const uint8_t* sroot, uint8_t* same, int64_t* plen,
-                     uint8_t* h_same, uint8_t* sstat, uint8_t* parent_flag, uint8_t* parent_id, uint32_t* data_offset,
-                     uint32_t* data_len, uint64_t present) {
-  constexpr size_t kRows = ag::kPipeShreds;
-  const size_t r0 = s * kRows, cw_stride = kRows * S;
-  uint8_t* cw = codewords + s * cw_stride;
-  ag::ShredColumns rc = cols;
-  rc.kind += r0;
-  rc.slot += r0;
-  rc.slice_index += r0;
-  rc.is_last += r0;
-  rc.shred_index += r0;
-  rc.data = cw;
-  rc.data_len += r0;
-  rc.sig += 64 * r0;
-  rc.proof += r0 * cols.proof_stride;
-  rc.height += r0;
-  if (ag::launch_shred_deserialize(packets + r0 * packet_stride, packet_stride, packet_lens + r0, kRows, rc, wire + r0,
-                                   c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  uint8_t dp[ag::kPipeData], cp[kRows - ag::kPipeData];
-  for (uint32_t j = 0; j < kRows; ++j) {
-    const uint8_t bit = static_cast<uint8_t>((present >> j) & 1);
-    if (j < ag::kPipeData) dp[j] = bit;
-    else cp[j - ag::kPipeData] = bit;
-  }
-  int st = ag_rs_coder_deshred_batch(c, kRows - ag::kPipeData, 1, S, cw, cw_stride, dp, cp, AG_RS_DECODE_EXACT, plen);
-  if (st) return st;
-  *h_same = 0;
-  if (*plen < 0) return AG_RS_OK;
-  if ((st = ag_merkle_build_batch(c, kRows, S, 1, cw, S, cw_stride, roots2 + 32 * s, nullptr, 0,
-                                  proof + r0 * cols.proof_stride, kRows * cols.proof_stride)))
-    return st;
-  if (ag::launch_pipe_root_cmp(roots2 + 32 * s, sroot + 32 * s, 1, same + s, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  AG_HIP(hipMemcpyAsync(h_same, same + s, 1, hipMemcpyDeviceToHost, c->stream));
-  // synchronous: h_same has landed when it returns
-  return ag_slice_parse_batch(c, 1, cw, cw_stride, plen, sstat, parent_flag, parent_id, data_offset, data_len);
-}
-
 }  // namespace
 
-namespace {
-// ag_slice_sign_batch on the context's side stream, forked from the main stream's current point
-// (the roots): the signing (one signature per lane, latency-bound) overlaps the serialization of
-// everything else in the datagrams; the caller waits on side_join before launch_shred_sig_patch.
-int sign_on_side(ag_rs_ctx* c, size_t n, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
-                 const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs) {
+namespace ag::host {
+// The whole batch in one range (the composed deshred's coder stage).  no_surplus: the caller
+// knows that no slice keeps more than 32 shreds and none keeps all 32 data shreds.
+int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                       int64_t* plen, size_t m, bool no_surplus) {
   int st;
-  if ((st = c->ensure_side_stream())) return st;
-  AG_HIP(hipEventRecord(c->side_fork, c->stream));
-  AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
-  std::swap(c->stream, c->side);
-  st = ag_slice_sign_batch(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs, nullptr);
-  std::swap(c->stream, c->side);
-  if (st) {
-    (void)hipStreamSynchronize(c->side);
+  if ((st = pipe_coder_reserve(c, n, m)) ||
+      (st = pipe_coder_enqueue(c, 0, n, S, cw, cw_stride, d_present, m, no_surplus)))
     return st;
-  }
-  AG_HIP(hipEventRecord(c->side_join, c->side));
-  return AG_RS_OK;
+  return pipe_coder_finish(c, n, plen);
 }
-}  // namespace
+// shred sizes pipe_coder_deshred decodes on the device: whole 64-byte chunks (any m of the
+// device-pattern path), or for 32:32 a last chunk of T = S mod 64 bytes -- T >= 16 always, a
+// shorter T when no slice needs the re-encode (no_reencode: no surplus shreds, no slice with
+// every data shred; the TAIL encode takes T >= 16 only)
+bool pipe_tail_ok(size_t S, size_t m, bool no_reencode) {
+  const size_t T = S % 64;
+  return T == 0 || (m == kDataShreds && S % 2 == 0 && (T >= 16 || no_reencode));
+}
+}  // namespace ag::host
 
 extern "C" {
-
-int ag_shredder_shred_batch(ag_rs_ctx* c, size_t nslices, size_t S, const uint8_t* parent_flags,
-                            const uint8_t* parent_ids, const uint8_t* data, size_t data_stride,
-                            const uint32_t* data_lens, const uint64_t* slots, const uint64_t* slice_indices,
-                            const uint8_t* is_last, const uint8_t* seed, const uint8_t* pk, uint8_t* codewords,
-                            uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets, size_t packet_stride,
-                            uint32_t* packet_lens) {
-  if (!c || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
-      (nslices && (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed ||
-                   !pk)))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return AG_RS_OK;
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  const size_t n = nslices, N = n * ag::kPipeShreds, cw_stride = ag::kPipeShreds * S;
-  // 1. Slice::payload_bytes into the data regions, 2. ReedSolomonCoder::shred in place
-  std::vector<uint32_t> lens(n);
-  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
-                                lens.data());
-  if (st) return st;
-  if ((st = ag_rs_coder_shred_batch(c, ag::kPipeShreds - ag::kPipeData, n, S, nullptr, 0, lens.data(), codewords,
-                                    cw_stride)))
-    return st;
-  // 3. slice Merkle trees: roots and every shred's path
-  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kind, *sidx, *dlen, *height;
-  if (!roots && (st = pipe_buf(c, 0, 32 * n, &roots))) return st;
-  if (!sigs && (st = pipe_buf(c, 1, 64 * n, &sigs))) return st;
-  if ((st = pipe_buf(c, 2, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, 3, N, &kind)) ||
-      (st = pipe_buf(c, 4, 4 * N, &sidx)) || (st = pipe_buf(c, 5, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, 6, 4 * N, &height)))
-    return st;
-  if ((st = ag_merkle_build_batch(c, ag::kPipeShreds, S, n, codewords, S, cw_stride, roots, nullptr, 0, proofs,
-                                  ag::kPipeShreds * kPipeProofBytes)))
-    return st;
-  // 4. slice_sig = sign(SliceCommitment(header, root))
-  // 4b. signed on the side stream while 5 serializes the rest of the datagrams
-  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
-  // 5. the 64 datagrams per slice (header and signature shared by the slice's rows)
-  ag::PipeExpandParams ep{};
-  ep.nslices = n;
-  ep.shred_bytes = static_cast<uint32_t>(S);
-  ep.num_data = ag::kPipeData;
-  ep.kind = kind;
-  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
-  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
-  ep.height = reinterpret_cast<uint32_t*>(height);
-  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  ag::ShredColumns cols{};
-  cols.kind = kind;
-  cols.slot = const_cast<uint64_t*>(slots);
-  cols.slice_index = const_cast<uint64_t*>(slice_indices);
-  cols.is_last = const_cast<uint8_t*>(is_last);
-  cols.shred_index = ep.shred_index;
-  cols.data = codewords;
-  cols.data_stride = S;
-  cols.data_len = ep.data_len;
-  cols.sig = sigs;
-  cols.proof = proofs;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = ep.height;
-  cols.hdr_group = ag::kPipeShreds;
-  cols.skip_sig = 1;
-  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(c->side);
-    return AG_RS_ERR_DEVICE;
-  }
-  AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  return AG_RS_OK;
-}
-
-// RegularShredder::shred over slices of mixed shred sizes: the stages of ag_shredder_shred_batch,
-// each taking one size per slice -- the var coder (one launch set for the whole mix), the var
-// Merkle build over the size table the coder uploaded (d_lens: lens | sizes | column prefix; it
-// stays valid on the stream until the next coder call), the serializer with a row size per slice.
-int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* parent_flags, const uint8_t* parent_ids,
-                                const uint8_t* data, size_t data_stride, const uint32_t* data_lens,
-                                const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
-                                const uint8_t* seed, const uint8_t* pk, uint8_t* codewords, size_t codeword_stride,
-                                uint32_t* shred_bytes_out, uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets,
-                                size_t packet_stride, uint32_t* packet_lens, size_t nblocks,
-                                const uint32_t* block_counts, uint8_t* block_hashes_out) {
-  if (!c || nslices >= (size_t{1} << 24)) return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return nblocks ? AG_RS_ERR_INVALID_ARGUMENT : AG_RS_OK;
-  if (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed || !pk ||
-      !codewords || !packets || !packet_lens || reinterpret_cast<uintptr_t>(codewords) % 16 || codeword_stride % 16)
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  const size_t n = nslices, N = n * ag::kPipeShreds;
-  // every check on the host, before the first launch: the framing's, the strides', the blocks'
-  std::vector<uint32_t> lens(n);
-  size_t max_s = 0, max_len = 0;
-  for (size_t b = 0; b < n; ++b) {
-    if (parent_flags[b] > 1) return AG_RS_ERR_INVALID_ARGUMENT;
-    const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
-    if (framed > AG_SLICE_MAX_DATA) return AG_RS_ERR_TOO_MUCH_DATA;
-    size_t S = 0;
-    if (ag_rs_coder_shred_bytes(framed, &S)) return AG_RS_ERR_TOO_MUCH_DATA;
-    max_s = std::max(max_s, S);
-    max_len = std::max<size_t>(max_len, data_lens[b]);
-  }
-  size_t need = 0;
-  if (ag_shred_datagram_bytes(max_s, ag::kPipeHeight, &need) || packet_stride < need ||
-      codeword_stride < ag::kPipeShreds * max_s || (max_len && (!data || (n > 1 && data_stride < max_len))))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nblocks) {
-    if (!block_counts || !block_hashes_out || reinterpret_cast<uintptr_t>(block_hashes_out) % 16 || nblocks > n)
-      return AG_RS_ERR_INVALID_ARGUMENT;
-    size_t sum = 0;
-    for (size_t b = 0; b < nblocks; ++b) {
-      if (block_counts[b] == 0 || block_counts[b] > AG_BLOCK_MAX_SLICES) return AG_RS_ERR_INVALID_ARGUMENT;
-      sum += block_counts[b];
-    }
-    if (sum != n) return AG_RS_ERR_INVALID_ARGUMENT;
-  }
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  // 1. Slice::payload_bytes into the data regions (a framed payload is shorter than 32 * S_s, so
-  //    it stays inside its own slice's data shreds), 2. ReedSolomonCoder::shred in place
-  int st = ag_slice_frame_batch(c, n, max_s, parent_flags, parent_ids, data, data_stride, data_lens, codewords,
-                                codeword_stride, lens.data());
-  if (st) return st;
-  if ((st = ag_rs_coder_shred_batch_var(c, ag::kPipeShreds - ag::kPipeData, n, nullptr, 0, lens.data(), codewords,
-                                        codeword_stride, shred_bytes_out)))
-    return st;
-  if (!(c->last_encode_kernels & ag::kEkVar)) return AG_RS_ERR_DEVICE;  // (16-byte-aligned codewords: always var)
-  const uint32_t* d_sizes = c->d_lens.as<uint32_t>() + n;
-  // 3. slice Merkle trees: roots and every shred's path
-  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kind, *sidx, *dlen, *height;
-  if (!roots && (st = pipe_buf(c, 0, 32 * n, &roots))) return st;
-  if (!sigs && (st = pipe_buf(c, 1, 64 * n, &sigs))) return st;
-  if ((st = pipe_buf(c, 2, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, 3, N, &kind)) ||
-      (st = pipe_buf(c, 4, 4 * N, &sidx)) || (st = pipe_buf(c, 5, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, 6, 4 * N, &height)))
-    return st;
-  if ((st = merkle_var_launch(c, n, d_sizes, codewords, codeword_stride, roots, nullptr, 0, proofs,
-                              ag::kPipeShreds * kPipeProofBytes)))
-    return st;
-  // 4. slice_sig = sign(SliceCommitment(header, root)), on the side stream while 5 serializes
-  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
-  // 5. the 64 datagrams per slice, rows and data lengths at the slice's own size
-  ag::PipeExpandParams ep{};
-  ep.nslices = n;
-  ep.num_data = ag::kPipeData;
-  ep.kind = kind;
-  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
-  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
-  ep.height = reinterpret_cast<uint32_t*>(height);
-  ep.slice_bytes = d_sizes;
-  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(c->side);
-    return AG_RS_ERR_DEVICE;
-  }
-  ag::ShredColumns cols{};
-  cols.kind = kind;
-  cols.slot = const_cast<uint64_t*>(slots);
-  cols.slice_index = const_cast<uint64_t*>(slice_indices);
-  cols.is_last = const_cast<uint8_t*>(is_last);
-  cols.shred_index = ep.shred_index;
-  cols.data = codewords;
-  cols.data_stride = AG_RS_MAX_DATA_PER_SHRED;
-  cols.group_stride = codeword_stride;
-  cols.row_sizes = d_sizes;
-  cols.data_len = ep.data_len;
-  cols.sig = sigs;
-  cols.proof = proofs;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = ep.height;
-  cols.hdr_group = ag::kPipeShreds;
-  cols.skip_sig = 1;
-  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(c->side);
-    return AG_RS_ERR_DEVICE;
-  }
-  // 6. the block hashes over the roots: a chain of dependent levels a few workgroups wide, placed
-  //    where the main stream would otherwise only wait for the signatures
-  if (nblocks && (st = ag_block_tree_batch(c, nblocks, block_counts, roots, block_hashes_out, nullptr, 0, nullptr, 0))) {
-    (void)hipStreamSynchronize(c->side);
-    return st;
-  }
-  AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  return AG_RS_OK;
-}
-
-int ag_shredder_deshred_batch(ag_rs_ctx* c, size_t nslices, size_t S, uint8_t* packets, size_t packet_stride,
-                              uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords, int32_t* status,
-                              uint64_t* slots_out, uint64_t* slice_indices_out, uint8_t* is_last_out,
-                              uint8_t* parent_flags_out, uint8_t* parent_ids_out, uint32_t* data_offsets_out,
-                              uint32_t* data_lens_out) {
-  if (!c || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
-      (nslices && (!pk || !status || !slots_out || !slice_indices_out || !is_last_out || !parent_flags_out ||
-                   !parent_ids_out || !data_offsets_out || !data_lens_out)))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return AG_RS_OK;
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  const size_t n = nslices, N = n * ag::kPipeShreds, cw_stride = ag::kPipeShreds * S;
-  int st;
-  // per-shred columns (payload rows straight into the codewords: row 64 s + j is shard j of slice s)
-  uint8_t *kind, *slot, *sidx, *last, *shidx, *dlen, *sig, *proof, *height, *wire, *vstat, *roots;
-  if ((st = pipe_buf(c, 0, N, &kind)) || (st = pipe_buf(c, 1, 8 * N, &slot)) || (st = pipe_buf(c, 2, 8 * N, &sidx)) ||
-      (st = pipe_buf(c, 3, N, &last)) || (st = pipe_buf(c, 4, 4 * N, &shidx)) || (st = pipe_buf(c, 5, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, 6, 64 * N, &sig)) || (st = pipe_buf(c, 7, kPipeProofBytes * N, &proof)) ||
-      (st = pipe_buf(c, 8, 4 * N, &height)) || (st = pipe_buf(c, 9, N, &wire)) || (st = pipe_buf(c, 10, N, &vstat)) ||
-      (st = pipe_buf(c, 11, 32 * N, &roots)))
-    return st;
-  ag::ShredColumns cols{};
-  cols.kind = kind;
-  cols.slot = reinterpret_cast<uint64_t*>(slot);
-  cols.slice_index = reinterpret_cast<uint64_t*>(sidx);
-  cols.is_last = last;
-  cols.shred_index = reinterpret_cast<uint32_t*>(shidx);
-  cols.data = codewords;
-  cols.data_stride = S;
-  cols.data_len = reinterpret_cast<uint32_t*>(dlen);
-  cols.sig = sig;
-  cols.proof = proof;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = reinterpret_cast<uint32_t*>(height);
-  // 1. network::deserialize (absent slots have length 0: malformed, never written)
-  if (ag::launch_shred_deserialize(packets, packet_stride, packet_lens, N, cols, wire, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  // 2. ValidatedShred::try_new: one signature per slice (its first plausible shred) ...
-  uint8_t *pick, *gdata, *gproof, *gslot, *gsidx, *glast, *gidx, *gsig, *pstat, *commits, *hasc;
-  if ((st = pipe_buf(c, 12, n, &pick)) || (st = pipe_buf(c, 13, n * S, &gdata)) ||
-      (st = pipe_buf(c, 14, kPipeProofBytes * n, &gproof)) || (st = pipe_buf(c, 15, 8 * n, &gslot)) ||
-      (st = pipe_buf(c, 16, 8 * n, &gsidx)) || (st = pipe_buf(c, 17, n, &glast)) || (st = pipe_buf(c, 18, 4 * n, &gidx)) ||
-      (st = pipe_buf(c, 19, 64 * n, &gsig)) || (st = pipe_buf(c, 20, n, &pstat)) ||
-      (st = pipe_buf(c, 21, ag::kSliceCommitmentLen * n, &commits)) || (st = pipe_buf(c, 22, n, &hasc)))
-    return st;
-  uint8_t* plaus;  // per shred: the datagram parsed and fits its slot
-  if ((st = pipe_buf(c, 24, N, &plaus))) return st;
-  ag::PipePickParams pp{};
-  pp.nslices = n;
-  pp.shred_bytes = static_cast<uint32_t>(S);
-  pp.num_data = ag::kPipeData;
-  pp.wire_status = wire;
-  pp.cols = cols;
-  pp.pick = pick;
-  pp.g_data = gdata;
-  pp.g_proof = gproof;
-  pp.g_slot = reinterpret_cast<uint64_t*>(gslot);
-  pp.g_slice_index = reinterpret_cast<uint64_t*>(gsidx);
-  pp.g_is_last = glast;
-  pp.g_shred_index = reinterpret_cast<uint32_t*>(gidx);
-  pp.g_sig = gsig;
-  pp.plausible = plaus;
-  AG_HIP(hipMemsetAsync(gdata, 0, n * S, c->stream));  // slices without a pick: defined bytes
-  AG_HIP(hipMemsetAsync(gidx, 0, 4 * n, c->stream));
-  if (ag::launch_pipe_pick(pp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  // every plausible shred's root (derive_root, with its leaf digest for the Merkle rebuild's level
-  // 0: step 5 hashes only the rows the coder restores or may rewrite) on the side stream: it needs
-  // only the parse and the pick's plausibility flags, so it overlaps the picked shreds'
-  // signature checks below (one signature per lane: a latency-bound kernel)
-  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
-  uint8_t* dlist;
-  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream)) || (st = c->ensure_side_stream()) ||
-      (st = pipe_buf(c, 26, 4 * (N + 1), &dlist)))
-    return st;
-  uint8_t* nodes = c->d_merkle_nodes.as<uint8_t>();
-  {
-    ag::MerkleVerifyParams mp{};
-    mp.leaves = codewords;
-    mp.leaf_stride = S;
-    mp.leaf_bytes = static_cast<uint32_t>(S);
-    mp.height = ag::kPipeHeight;
-    mp.index = cols.shred_index;
-    mp.proofs = proof;
-    mp.proofs_stride = kPipeProofBytes;
-    mp.n = N;
-    mp.roots_out = roots;
-    mp.active = plaus;
-    mp.list = reinterpret_cast<uint32_t*>(dlist);
-    mp.leaf_nodes = nodes;
-    mp.leaf_nodes_stride = nodes_stride;
-    mp.leaves_per_tree = ag::kPipeShreds;
-    AG_HIP(hipEventRecord(c->side_fork, c->stream));
-    AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
-    if (ag::launch_merkle_verify(mp, c->side) != hipSuccess) return AG_RS_ERR_DEVICE;
-    AG_HIP(hipEventRecord(c->side_join, c->side));
-  }
-  if ((st = shred_validate_impl(c, n, gdata, S, S, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
-                                pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, nullptr, pstat,
-                                nullptr, commits))) {
-    (void)hipStreamSynchronize(c->side);
-    return st;
-  }
-  if (ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  // ... then every shred against its slice's commitment (signature only without a cache)
-  AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-  if ((st = shred_validate_impl(c, N, codewords, S, S, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
-                                cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds, plaus,
-                                vstat, roots, nullptr, nodes, nodes_stride, ag::kPipeShreds, 0, 0, true)))
-    return st;
-  // 3. per slice: the shreds kept, the root, header and signature
-  uint8_t* per_slice;
-  if ((st = pipe_buf(c, 23, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice))) return st;
-  // 32-byte rows first: the Merkle build wants 16-byte aligned roots
-  uint8_t* sroot = per_slice;
-  uint8_t* roots2 = sroot + 32 * n;
-  uint8_t* ssig = roots2 + 32 * n;
-  uint64_t* d_present = reinterpret_cast<uint64_t*>(ssig + 64 * n);
-  uint64_t* d_slot = d_present + n;
-  uint8_t* ssidx = reinterpret_cast<uint8_t*>(d_slot + n);
-  uint8_t* slast = ssidx + 8 * n;
-  ag::PipeCheckParams kp{};
-  kp.nslices = n;
-  kp.shred_bytes = static_cast<uint32_t>(S);
-  kp.num_data = ag::kPipeData;
-  kp.wire_status = wire;
-  kp.val_status = vstat;
-  kp.roots = roots;
-  kp.cols = cols;
-  kp.present = d_present;
-  kp.root = sroot;
-  kp.slot = d_slot;
-  kp.slice_index = reinterpret_cast<uint64_t*>(ssidx);
-  kp.is_last = slast;
-  kp.sig = ssig;
-  if (ag::launch_pipe_check(kp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  PipeMeta hm;
-  if ((st = read_pipe_meta(c, d_present, n, &hm))) return st;
-  const uint64_t *h_present = hm.present, *h_slot = hm.slot, *h_sidx = hm.sidx;
-  const uint8_t* h_last = hm.last;
-  // 4. ReedSolomonCoder::deshred over the kept shreds (restores the data shreds, re-encodes
-  //    all coding shreds, strips the padding); on the device for whole-chunk shreds
-  std::vector<int64_t> plen(n);
-  bool no_reencode = true;  // no surplus shreds and no slice with every data shred
-  for (size_t s = 0; s < n && no_reencode; ++s)
-    no_reencode = __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData) &&
-                  (h_present[s] & 0xFFFFFFFFull) != 0xFFFFFFFFull;
-  const bool device_coder = pipe_tail_ok(S, kDataShreds, no_reencode);
-  if (device_coder) {
-    if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, d_present, plen.data(), kDataShreds, no_reencode)))
-      return st;
-  } else {
-    std::vector<uint8_t> dp(n * ag::kPipeData), cp(n * (ag::kPipeShreds - ag::kPipeData));
-    for (size_t s = 0; s < n; ++s)
-      for (uint32_t j = 0; j < ag::kPipeShreds; ++j) {
-        const uint8_t bit = static_cast<uint8_t>((h_present[s] >> j) & 1);
-        if (j < ag::kPipeData) dp[s * ag::kPipeData + j] = bit;
-        else cp[s * (ag::kPipeShreds - ag::kPipeData) + j - ag::kPipeData] = bit;
-      }
-    if ((st = ag_rs_coder_deshred_batch(c, ag::kPipeShreds - ag::kPipeData, n, S, codewords, cw_stride, dp.data(),
-                                        cp.data(), AG_RS_DECODE_ANY_K, plen.data())))
-      return st;
-  }
-  // 5. check_merkle_tree: the rebuilt tree's root must be the signed one; its paths serve
-  //    the reconstructed datagrams.  Kept shreds the coder left as received reuse the digests
-  //    their proof check computed (same bytes); restored rows, and coding rows the re-encode
-  //    may have rewritten, are hashed again.
-  //    Invariant the reuse depends on: present ⊆ active ∧ proof-ok.  Every kept
-  //    shred (a bit of d_present, set by pipe_check only for shreds that were active in the
-  //    step-3 verify and whose derived root matched) had its leaf digest written to
-  //    d_merkle_nodes at (slice, index) by that verify; nothing between step 3 and here writes
-  //    those rows of the codeword or those nodes (the coder stage touches only absent rows
-  //    and, per the store masks, coding rows the leaf flags mark for re-hashing).  The verify
-  //    also stores digests of rows it then rejects: those rows are not in d_present, so the
-  //    flags below re-hash or ignore them.  A new step in between that writes kept rows or
-  //    d_merkle_nodes must clear the matching present bits or re-hash.
-  {
-    uint8_t *lflags, *llist;
-    if ((st = pipe_buf(c, 25, N, &lflags)) || (st = pipe_buf(c, 26, 4 * (N + 1), &llist)) ||
-        (st = ensure_empty_roots(c)))
-      return st;
-    // the host coder path (shreds not whole 64-byte chunks) re-encodes every coding shred
-    if (ag::launch_pipe_leaf_flags(d_present, n, !device_coder, lflags, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    ag::MerkleBuildParams mb{};
-    mb.leaves = codewords;
-    mb.leaf_stride = S;
-    mb.slice_stride = cw_stride;
-    mb.leaf_bytes = static_cast<uint32_t>(S);
-    mb.n_leaves = ag::kPipeShreds;
-    mb.nslices = n;
-    mb.empty_roots = c->d_empty_roots.as<uint32_t>();
-    mb.roots = roots2;
-    mb.proofs = proof;
-    mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
-    mb.hash_leaf = lflags;
-    mb.list = reinterpret_cast<uint32_t*>(llist);
-    c->last_merkle_kernels = 0;
-    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-  }
-  uint8_t* same = pstat;  // first validation's statuses are dead
-  if (ag::launch_pipe_root_cmp(roots2, sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  std::vector<uint8_t> h_same(n);
-  AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
-  // 6. SlicePayload::try_from
-  std::vector<uint8_t> sstat(n);
-  if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
-                                 parent_ids_out, data_offsets_out, data_lens_out)))
-    return st;  // synchronous: h_same has landed
-  // 6b. The crate's decoder reads every kept shred (reed_solomon.rs:154-166); the pass above
-  //     reads 32 of them (ANY_K).  On a consistent slice both restore the same bytes (MDS), and
-  //     a slice that passed check_merkle_tree is consistent: the rebuilt codeword matches the
-  //     signed root that commits every kept shred.  A slice that failed the padding or the
-  //     Merkle check with more than 32 kept shreds may hold an inconsistent shred the ANY_K
-  //     pass did not read (a leader signing a non-codeword), and the crate's bytes -- hence
-  //     the error, BadEncoding vs InvalidMerkleTree -- can differ.  Such slices are decoded
-  //     again from their received bytes with EXACT and re-checked, one by one (honest
-  //     leaders never produce them).
-  for (size_t s = 0; s < n; ++s) {
-    const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
-    if (!failed || __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData)) continue;
-    if ((st = pipe_rerun_exact(c, s, S, packets, packet_stride, packet_lens, cols, wire, codewords, proof, roots2,
-                               sroot, same, &plen[s], &h_same[s], &sstat[s], parent_flags_out + s,
-                               parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s, data_offsets_out + s,
-                               data_lens_out + s, h_present[s])))
-      return st;
-  }
-  std::vector<uint8_t> ok(n);
-  for (size_t s = 0; s < n; ++s) {
-    int32_t r = AG_RS_OK;
-    if (plen[s] < 0) {
-      r = -plen[s] == AG_RS_ERR_INVALID_PADDING ? AG_RS_ERR_BAD_ENCODING : static_cast<int32_t>(-plen[s]);
-    } else if (!h_same[s]) {
-      r = AG_RS_ERR_INVALID_MERKLE_TREE;
-    } else if (sstat[s] == AG_SLICE_TOO_LARGE) {
-      r = AG_RS_ERR_TOO_MUCH_DATA;
-    } else if (sstat[s] != AG_SLICE_OK) {
-      r = AG_RS_ERR_BAD_ENCODING;
-    }
-    status[s] = r;
-    ok[s] = r == AG_RS_OK;
-    slots_out[s] = ok[s] ? h_slot[s] : 0;
-    slice_indices_out[s] = ok[s] ? h_sidx[s] : 0;
-    is_last_out[s] = ok[s] ? h_last[s] : 0;
-  }
-  // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
-  uint8_t *d_ok, *fresh;
-  if ((st = pipe_buf(c, 20, n, &d_ok)) || (st = pipe_buf(c, 10, 4 * N, &fresh))) return st;
-  AG_HIP(hipMemcpyAsync(d_ok, ok.data(), n, hipMemcpyHostToDevice, c->stream));
-  ag::PipeExpandParams ep{};
-  ep.nslices = n;
-  ep.shred_bytes = static_cast<uint32_t>(S);
-  ep.num_data = ag::kPipeData;
-  ep.skip = d_present;
-  ep.slice_ok = d_ok;
-  ep.kind = kind;
-  ep.shred_index = cols.shred_index;
-  ep.data_len = cols.data_len;
-  ep.height = cols.height;
-  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  ag::ShredColumns fc = cols;
-  fc.slot = d_slot;
-  fc.slice_index = reinterpret_cast<uint64_t*>(ssidx);
-  fc.is_last = slast;
-  fc.sig = ssig;
-  fc.hdr_group = ag::kPipeShreds;
-  if (ag::launch_shred_serialize(fc, N, packets, packet_stride, reinterpret_cast<uint32_t*>(fresh), c->stream) !=
-          hipSuccess ||
-      ag::launch_pipe_merge_lens(reinterpret_cast<uint32_t*>(fresh), d_present, d_ok, n, packet_lens, c->stream) !=
-          hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  AG_HIP(hipStreamSynchronize(c->stream));  // host vectors read by async copies
-  return AG_RS_OK;
-}
-
-
-// ---- the other three shredders of shredder.rs composed (CodingOnly, PETS, AONT) -------------
-// (outside extern "C": helpers)
-}  // extern "C"
-
-namespace {
-// Output shred j of a slice <-> codeword row (data rows 0..31, coding rows 32..32+m-1):
-// Regular / AONT: j; CodingOnly: 32 + j (the 64 coding shreds, no data shreds: shredder.rs:
-// 367-376); PETS: j for j < 31, j + 1 after (the data shred holding the key withheld,
-// :414-422).  The pipeline addresses the output rows in the caller's codeword buffer itself
-// (grouped_row_offset: base row row0, slice stride cw_stride, row `skip` and later one shard
-// further), so no row is copied between the coder's layout and the datagrams'.
-struct ShredderKind {
-  uint32_t m;         // coding shreds of the coder (ReedSolomonCoder::new(CODING_OUTPUT_SHREDS))
-  uint32_t num_data;  // DATA_OUTPUT_SHREDS
-  int aon;            // AG_AON_* or -1
-  uint32_t row0;      // codeword row of output shred 0
-  uint32_t skip;      // output shreds >= skip sit one row further (0: none)
-};
-bool shredder_kind(int kind, ShredderKind* k) {
-  switch (kind) {
-    case AG_SHREDDER_CODING_ONLY: *k = {64, 0, -1, kDataShreds, 0}; return true;
-    case AG_SHREDDER_PETS: *k = {33, 31, AG_AON_PETS, 0, 31}; return true;
-    case AG_SHREDDER_AONT: *k = {32, 32, AG_AON_AONT, 0, 0}; return true;
-    default: return false;
-  }
-}
-uint32_t kind_row(const ShredderKind& k, uint32_t j) { return k.row0 + j + (k.skip && j >= k.skip ? 1u : 0u); }
-// the Merkle tree over the 64 output rows of each slice: roots, proofs (nodes in context scratch)
-int kind_merkle(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint8_t* codewords, size_t cw_stride,
-                uint8_t* roots, uint8_t* proofs) {
-  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
-  int st;
-  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream)) || (st = ensure_empty_roots(c))) return st;
-  ag::MerkleBuildParams mb{};
-  mb.leaves = codewords + k.row0 * S;
-  mb.leaf_stride = S;
-  mb.slice_stride = cw_stride;
-  mb.skip_leaf = k.skip;
-  mb.leaf_bytes = static_cast<uint32_t>(S);
-  mb.n_leaves = ag::kPipeShreds;
-  mb.nslices = n;
-  mb.empty_roots = c->d_empty_roots.as<uint32_t>();
-  mb.roots = roots;
-  mb.proofs = proofs;
-  mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
-  c->last_merkle_kernels = 0;
-  return ag::launch_merkle_build(mb, c->d_merkle_nodes.as<uint8_t>(), nodes_stride, c->stream,
-                                 &c->last_merkle_kernels) == hipSuccess
-             ? AG_RS_OK
-             : AG_RS_ERR_DEVICE;
-}
-void kind_rows(const ShredderKind& k, uint8_t* codewords, size_t S, size_t cw_stride, ag::ShredColumns* cols) {
-  cols->data = codewords + k.row0 * S;
-  cols->data_stride = S;
-  cols->group_stride = cw_stride;
-  cols->skip_row = k.skip;
-}
-}  // namespace
-
-extern "C" {
-
-int ag_shredder_shred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_t S, const uint8_t* parent_flags,
-                                 const uint8_t* parent_ids, const uint8_t* data, size_t data_stride,
-                                 const uint32_t* data_lens, const uint64_t* slots, const uint64_t* slice_indices,
-                                 const uint8_t* is_last, const uint8_t* seed, const uint8_t* pk, const uint8_t* keys,
-                                 uint8_t* codewords, size_t cw_stride, uint8_t* roots_out, uint8_t* sigs_out,
-                                 uint8_t* packets, size_t packet_stride, uint32_t* packet_lens) {
-  if (kind == AG_SHREDDER_REGULAR) {
-    if (cw_stride != ag::kPipeShreds * S) return AG_RS_ERR_INVALID_ARGUMENT;
-    return ag_shredder_shred_batch(c, nslices, S, parent_flags, parent_ids, data, data_stride, data_lens, slots,
-                                   slice_indices, is_last, seed, pk, codewords, roots_out, sigs_out, packets,
-                                   packet_stride, packet_lens);
-  }
-  ShredderKind k;
-  if (!c || !shredder_kind(kind, &k) || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
-      cw_stride < (kDataShreds + k.m) * S || cw_stride % 4 ||
-      (nslices && (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed ||
-                   !pk || (k.aon >= 0 && !keys))))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return AG_RS_OK;
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  const size_t n = nslices, N = n * ag::kPipeShreds;
-  // MAX_DATA_SIZE: the key tail of PETS / AONT must fit the slice as well (shredder.rs:409, 457)
-  const size_t extra = k.aon >= 0 ? ag::kCipherKeyBytes : 0;
-  for (size_t b = 0; b < n; ++b) {
-    const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
-    if (framed + extra > kMaxPayload) return AG_RS_ERR_TOO_MUCH_DATA;
-  }
-  // 1. Slice::payload_bytes into the data regions; 2. PETS / AONT: encrypt_with_random_key with
-  //    the caller's key + the key tail; 3. ReedSolomonCoder::shred in place
-  std::vector<uint32_t> lens(n);
-  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
-                                lens.data());
-  if (st) return st;
-  if (k.aon >= 0) {
-    if ((st = ag_aon_encrypt_batch(c, k.aon, n, keys, codewords, cw_stride, lens.data()))) return st;
-    for (uint32_t& l : lens) l += static_cast<uint32_t>(ag::kCipherKeyBytes);
-  }
-  if ((st = ag_rs_coder_shred_batch(c, k.m, n, S, nullptr, 0, lens.data(), codewords, cw_stride))) return st;
-  // 4. the 64 output shreds (data first) in place: Merkle tree, signature, datagrams over them
-  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kcol, *sidx, *dlen, *height;
-  if (!roots && (st = pipe_buf(c, 0, 32 * n, &roots))) return st;
-  if (!sigs && (st = pipe_buf(c, 1, 64 * n, &sigs))) return st;
-  if ((st = pipe_buf(c, 2, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, 3, N, &kcol)) ||
-      (st = pipe_buf(c, 4, 4 * N, &sidx)) || (st = pipe_buf(c, 5, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, 6, 4 * N, &height)))
-    return st;
-  if ((st = kind_merkle(c, k, n, S, codewords, cw_stride, roots, proofs))) return st;
-  // 4b. signed on the side stream while 5 serializes the rest of the datagrams
-  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
-  ag::PipeExpandParams ep{};
-  ep.nslices = n;
-  ep.shred_bytes = static_cast<uint32_t>(S);
-  ep.num_data = k.num_data;
-  ep.kind = kcol;
-  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
-  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
-  ep.height = reinterpret_cast<uint32_t*>(height);
-  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  ag::ShredColumns cols{};
-  cols.kind = kcol;
-  cols.slot = const_cast<uint64_t*>(slots);
-  cols.slice_index = const_cast<uint64_t*>(slice_indices);
-  cols.is_last = const_cast<uint8_t*>(is_last);
-  cols.shred_index = ep.shred_index;
-  kind_rows(k, codewords, S, cw_stride, &cols);
-  cols.data_len = ep.data_len;
-  cols.sig = sigs;
-  cols.proof = proofs;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = ep.height;
-  cols.hdr_group = ag::kPipeShreds;
-  cols.skip_sig = 1;
-  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(c->side);
-    return AG_RS_ERR_DEVICE;
-  }
-  AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  return AG_RS_OK;
-}
-
-int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_t S, uint8_t* packets,
-                                   size_t packet_stride, uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords,
-                                   size_t cw_stride, int32_t* status, uint64_t* slots_out, uint64_t* slice_indices_out,
-                                   uint8_t* is_last_out, uint8_t* parent_flags_out, uint8_t* parent_ids_out,
-                                   uint32_t* data_offsets_out, uint32_t* data_lens_out) {
-  if (kind == AG_SHREDDER_REGULAR) {
-    if (cw_stride != ag::kPipeShreds * S) return AG_RS_ERR_INVALID_ARGUMENT;
-    return ag_shredder_deshred_batch(c, nslices, S, packets, packet_stride, packet_lens, pk, codewords, status,
-                                     slots_out, slice_indices_out, is_last_out, parent_flags_out, parent_ids_out,
-                                     data_offsets_out, data_lens_out);
-  }
-  ShredderKind k;
-  if (!c || !shredder_kind(kind, &k) || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
-      cw_stride < (kDataShreds + k.m) * S || cw_stride % 4 ||
-      (nslices && (!pk || !status || !slots_out || !slice_indices_out || !is_last_out || !parent_flags_out ||
-                   !parent_ids_out || !data_offsets_out || !data_lens_out)))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return AG_RS_OK;
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  const size_t n = nslices, N = n * ag::kPipeShreds;
-  int st;
-  // per-shred columns; payloads parsed straight into their codeword rows
-  uint8_t *kcol, *slot, *sidx, *last, *shidx, *dlen, *sig, *proof, *height, *wire, *vstat, *roots;
-  if ((st = pipe_buf(c, 0, N, &kcol)) || (st = pipe_buf(c, 1, 8 * N, &slot)) ||
-      (st = pipe_buf(c, 2, 8 * N, &sidx)) || (st = pipe_buf(c, 3, N, &last)) || (st = pipe_buf(c, 4, 4 * N, &shidx)) ||
-      (st = pipe_buf(c, 5, 4 * N, &dlen)) || (st = pipe_buf(c, 6, 64 * N, &sig)) ||
-      (st = pipe_buf(c, 7, kPipeProofBytes * N, &proof)) || (st = pipe_buf(c, 8, 4 * N, &height)) ||
-      (st = pipe_buf(c, 9, N, &wire)) || (st = pipe_buf(c, 10, N, &vstat)) || (st = pipe_buf(c, 11, 32 * N, &roots)))
-    return st;
-  ag::ShredColumns cols{};
-  cols.kind = kcol;
-  cols.slot = reinterpret_cast<uint64_t*>(slot);
-  cols.slice_index = reinterpret_cast<uint64_t*>(sidx);
-  cols.is_last = last;
-  cols.shred_index = reinterpret_cast<uint32_t*>(shidx);
-  kind_rows(k, codewords, S, cw_stride, &cols);
-  cols.data_len = reinterpret_cast<uint32_t*>(dlen);
-  cols.sig = sig;
-  cols.proof = proof;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = reinterpret_cast<uint32_t*>(height);
-  // Pass 0 decodes with ANY_K on the device (per-slice window patterns, no host per-slice work);
-  // a slice with surplus kept shreds that then fails some check could decode differently under
-  // the crate's decoder over every kept shred, so the batch is redone with EXACT (pass 1).  A
-  // slice that passes every check decoded the codeword its signed root commits, which every
-  // kept shred matches: EXACT agrees there.  The packets' lengths change only
-  // in step 7 (PETS / AONT serialize the absent datagrams before decrypting, into length-0 slots
-  // that a redo parses as absent), so the redo starts from the same datagrams.
-  const uint64_t *h_present = nullptr, *h_slot = nullptr, *h_sidx = nullptr;
-  const uint8_t* h_last = nullptr;
-  std::vector<uint8_t> ok(n), pre_ok(n);
-  uint64_t* d_present = nullptr;
-  uint8_t *sroot = nullptr, *ssig = nullptr, *ssidx = nullptr, *slast = nullptr, *fresh = nullptr;
-  uint64_t* d_slot = nullptr;
-  const bool fast_ok = pipe_tail_ok(S, k.m, true) && n > 1 && k.m >= kDataShreds && k.m <= 2 * kDataShreds;
-  // 7. fill_missing_shreds (part 1): the absent datagrams of the slices in `okv`, lengths into
-  // `fresh` (pipe_merge_lens moves the final slices' lengths into packet_lens)
-  auto serialize_absent = [&](const std::vector<uint8_t>& okv) -> int {
-    uint8_t* d_ok;
-    int e;
-    if ((e = pipe_buf(c, 20, n, &d_ok)) || (e = pipe_buf(c, 26, 4 * N, &fresh))) return e;
-    AG_HIP(hipMemcpyAsync(d_ok, okv.data(), n, hipMemcpyHostToDevice, c->stream));
-    ag::PipeExpandParams ep{};
-    ep.nslices = n;
-    ep.shred_bytes = static_cast<uint32_t>(S);
-    ep.num_data = k.num_data;
-    ep.skip = d_present;
-    ep.slice_ok = d_ok;
-    ep.kind = kcol;
-    ep.shred_index = cols.shred_index;
-    ep.data_len = cols.data_len;
-    ep.height = cols.height;
-    if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    ag::ShredColumns fc = cols;
-    fc.slot = d_slot;
-    fc.slice_index = reinterpret_cast<uint64_t*>(ssidx);
-    fc.is_last = slast;
-    fc.sig = ssig;
-    fc.hdr_group = ag::kPipeShreds;
-    if (ag::launch_shred_serialize(fc, N, packets, packet_stride, reinterpret_cast<uint32_t*>(fresh), c->stream) !=
-        hipSuccess)
-      return AG_RS_ERR_DEVICE;
-    // (okv is host memory the upload reads: the caller synchronizes before it changes)
-    AG_HIP(hipStreamSynchronize(c->stream));
-    return AG_RS_OK;
-  };
-  for (int pass = fast_ok ? 0 : 1; pass < 2; ++pass) {
-    // 1. network::deserialize
-    if (ag::launch_shred_deserialize(packets, packet_stride, packet_lens, N, cols, wire, c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-    // 2. ValidatedShred::try_new with the blockstore's cached commitment (the Regular pipeline's
-    //    steps 2-3 with this shredder's data / coding layout)
-    uint8_t *pick, *gdata, *gproof, *gslot, *gsidx, *glast, *gidx, *gsig, *pstat, *commits, *hasc, *plaus;
-    if ((st = pipe_buf(c, 12, n, &pick)) || (st = pipe_buf(c, 13, n * S, &gdata)) ||
-        (st = pipe_buf(c, 14, kPipeProofBytes * n, &gproof)) || (st = pipe_buf(c, 15, 8 * n, &gslot)) ||
-        (st = pipe_buf(c, 16, 8 * n, &gsidx)) || (st = pipe_buf(c, 17, n, &glast)) || (st = pipe_buf(c, 18, 4 * n, &gidx)) ||
-        (st = pipe_buf(c, 19, 64 * n, &gsig)) || (st = pipe_buf(c, 21, ag::kSliceCommitmentLen * n, &commits)) ||
-        (st = pipe_buf(c, 22, n, &hasc)) || (st = pipe_buf(c, 24, N, &plaus)) || (st = pipe_buf(c, 27, n, &pstat)))
-      return st;
-    ag::PipePickParams pp{};
-    pp.nslices = n;
-    pp.shred_bytes = static_cast<uint32_t>(S);
-    pp.num_data = k.num_data;
-    pp.wire_status = wire;
-    pp.cols = cols;
-    pp.pick = pick;
-    pp.g_data = gdata;
-    pp.g_proof = gproof;
-    pp.g_slot = reinterpret_cast<uint64_t*>(gslot);
-    pp.g_slice_index = reinterpret_cast<uint64_t*>(gsidx);
-    pp.g_is_last = glast;
-    pp.g_shred_index = reinterpret_cast<uint32_t*>(gidx);
-    pp.g_sig = gsig;
-    pp.plausible = plaus;
-    AG_HIP(hipMemsetAsync(gdata, 0, n * S, c->stream));
-    AG_HIP(hipMemsetAsync(gidx, 0, 4 * n, c->stream));
-    if (ag::launch_pipe_pick(pp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    // every plausible shred's root on the side stream, overlapping the picked shreds' signature
-    // checks (as the Regular pipeline)
-    uint8_t* dlist;
-    if ((st = c->ensure_side_stream()) || (st = pipe_buf(c, 25, 4 * (N + 1), &dlist))) return st;
-    {
-      ag::MerkleVerifyParams mp{};
-      mp.leaves = cols.data;
-      mp.leaf_stride = S;
-      mp.leaf_bytes = static_cast<uint32_t>(S);
-      mp.height = ag::kPipeHeight;
-      mp.index = cols.shred_index;
-      mp.proofs = proof;
-      mp.proofs_stride = kPipeProofBytes;
-      mp.n = N;
-      mp.roots_out = roots;
-      mp.active = plaus;
-      mp.list = reinterpret_cast<uint32_t*>(dlist);
-      mp.group_stride = cw_stride;
-      mp.skip_row = k.skip;
-      AG_HIP(hipEventRecord(c->side_fork, c->stream));
-      AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
-      if (ag::launch_merkle_verify(mp, c->side) != hipSuccess) return AG_RS_ERR_DEVICE;
-      AG_HIP(hipEventRecord(c->side_join, c->side));
-    }
-    if ((st = shred_validate_impl(c, n, gdata, S, S, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
-                                  pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, nullptr, pstat,
-                                  nullptr, commits))) {
-      (void)hipStreamSynchronize(c->side);
-      return st;
-    }
-    if (ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-    if ((st = shred_validate_impl(c, N, cols.data, S, S, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
-                                  cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds, plaus,
-                                  vstat, roots, nullptr, nullptr, 0, 0, cw_stride, k.skip, true)))
-      return st;
-    // 3. per slice: the shreds kept, the root, header and signature
-    uint8_t* per_slice;
-    if ((st = pipe_buf(c, 23, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice))) return st;
-    sroot = per_slice;
-    uint8_t* roots2 = sroot + 32 * n;
-    ssig = roots2 + 32 * n;
-    d_present = reinterpret_cast<uint64_t*>(ssig + 64 * n);
-    d_slot = d_present + n;
-    ssidx = reinterpret_cast<uint8_t*>(d_slot + n);
-    slast = ssidx + 8 * n;
-    ag::PipeCheckParams kp{};
-    kp.nslices = n;
-    kp.shred_bytes = static_cast<uint32_t>(S);
-    kp.num_data = k.num_data;
-    kp.wire_status = wire;
-    kp.val_status = vstat;
-    kp.roots = roots;
-    kp.cols = cols;
-    kp.present = d_present;
-    kp.root = sroot;
-    kp.slot = d_slot;
-    kp.slice_index = reinterpret_cast<uint64_t*>(ssidx);
-    kp.is_last = slast;
-    kp.sig = ssig;
-    if (ag::launch_pipe_check(kp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    PipeMeta hm;
-    if ((st = read_pipe_meta(c, d_present, n, &hm))) return st;
-    h_present = hm.present;
-    h_slot = hm.slot;
-    h_sidx = hm.sidx;
-    h_last = hm.last;
-    // 4. deshred_validated_shreds: ReedSolomonCoder::deshred over the kept shreds (in their
-    //    codeword rows already), then decrypt_payload (PETS / AONT) after the raw shreds are
-    //    taken.  Pass 0: ANY_K with the window patterns built on the device from the kept
-    //    shreds' codeword-row words; pass 1: the crate's decoder over every kept shred (EXACT)
-    std::vector<int64_t> plen(n);
-    bool surplus = false;
-    for (size_t s = 0; s < n; ++s) surplus |= __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
-    bool full_data = false;
-    if (kind == AG_SHREDDER_AONT)
-      for (size_t s = 0; s < n; ++s) full_data |= (h_present[s] & 0xFFFFFFFFull) == 0xFFFFFFFFull;
-    if (pass == 0 && pipe_tail_ok(S, k.m, !surplus && !full_data)) {
-      // codeword-row present words (pipe_coder_deshred: data | coding 0..31 << 32, coding
-      // 32..63 in word 1 when m > 32); AONT's rows are the codeword rows
-      const size_t wps = k.m > kDataShreds ? 2 : 1;
-      const uint64_t* words = d_present;
-      if (kind != AG_SHREDDER_AONT) {
-        uint8_t* dw;
-        if ((st = pipe_buf(c, 25, 8 * wps * n, &dw)) || (st = c->h_strip.ensure(8 * wps * n))) return st;
-        uint64_t* hw = c->h_strip.as<uint64_t>();
-        for (size_t s = 0; s < n; ++s) {
-          const uint64_t o = h_present[s];
-          if (kind == AG_SHREDDER_CODING_ONLY) {  // output j = coding j
-            hw[2 * s] = (o & 0xFFFFFFFFull) << 32;
-            hw[2 * s + 1] = o >> 32;
-          } else {  // PETS: output j < 31 = data j, output 31 + i = coding i
-            hw[2 * s] = (o & 0x7FFFFFFFull) | (((o >> 31) & 0xFFFFFFFFull) << 32);
-            hw[2 * s + 1] = o >> 63;
-          }
-        }
-        AG_HIP(hipMemcpyAsync(dw, hw, 8 * wps * n, hipMemcpyHostToDevice, c->stream));
-        words = reinterpret_cast<const uint64_t*>(dw);
-      }
-      // (pipe_coder_deshred reads its results back through h_strip after the upload completed)
-      if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, words, plen.data(), k.m, !surplus && !full_data)))
-        return st;
-    } else {
-      std::vector<uint8_t> dp(n * kDataShreds, 0), cp(n * k.m, 0);
-      for (size_t s = 0; s < n; ++s)
-        for (uint32_t j = 0; j < ag::kPipeShreds; ++j) {
-          const uint32_t r = kind_row(k, j);
-          const uint8_t bit = static_cast<uint8_t>((h_present[s] >> j) & 1);
-          if (r < kDataShreds) dp[s * kDataShreds + r] = bit;
-          else cp[s * k.m + (r - kDataShreds)] = bit;
-        }
-      if ((st = ag_rs_coder_deshred_batch(c, k.m, n, S, codewords, cw_stride, dp.data(), cp.data(), AG_RS_DECODE_EXACT,
-                                          plen.data())))
-        return st;
-    }
-    // AONT: the SHA-256 of every decoded ciphertext (decrypt_payload's key mask) runs on the side
-    // stream, overlapping the Merkle rebuild, the root comparison and the absent datagrams'
-    // serialization below (all of them only read the rows); one SHA-256 chain per slice leaves
-    // most of the chip's issue slots to them
-    bool sha_side = false;
-    if (k.aon == AG_AON_AONT) {
-      std::vector<uint32_t> shl(n);
-      uint32_t mx = ag::kCipherKeyBytes;
-      for (size_t s = 0; s < n; ++s) {
-        shl[s] = plen[s] >= static_cast<int64_t>(ag::kCipherKeyBytes) ? static_cast<uint32_t>(plen[s])
-                                                                      : static_cast<uint32_t>(ag::kCipherKeyBytes);
-        mx = std::max(mx, shl[s]);
-      }
-      if ((st = c->ensure_side_stream()) || (st = c->d_aon_lens2.ensure(n * 4, c->stream)) ||
-          (st = c->d_aon_digests.ensure(n * 32, c->stream)))
-        return st;
-      AG_HIP(hipStreamSynchronize(c->stream));
-      AG_HIP(hipMemcpy(c->d_aon_lens2.ptr, shl.data(), n * 4, hipMemcpyHostToDevice));
-      ag::BufferBatch sb;
-      sb.base = codewords;
-      sb.stride = cw_stride;
-      sb.lens = c->d_aon_lens2.as<uint32_t>();
-      sb.n = n;
-      sb.max_len = mx;
-      AG_HIP(hipEventRecord(c->side_fork, c->stream));
-      AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
-      if (ag::launch_sha256(sb, ag::kCipherKeyBytes, c->d_aon_digests.as<uint8_t>(), c->side) != hipSuccess)
-        return AG_RS_ERR_DEVICE;
-      AG_HIP(hipEventRecord(c->side_join, c->side));
-      sha_side = true;
-    }
-    // 5. check_merkle_tree over the raw output shreds (before any decryption: they are the
-    //    codeword rows)
-    if ((st = kind_merkle(c, k, n, S, codewords, cw_stride, roots2, proof))) return st;
-    uint8_t* same = pstat;
-    if (ag::launch_pipe_root_cmp(roots2, sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    std::vector<uint8_t> h_same(n);
-    AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
-    AG_HIP(hipStreamSynchronize(c->stream));
-    if (k.aon >= 0) {
-      // the absent datagrams of the slices that decoded and match their root, serialized from
-      // the encrypted rows; then decrypt_payload (BadEncoding for a failed key check)
-      for (size_t s = 0; s < n; ++s) pre_ok[s] = plen[s] >= 0 && h_same[s];
-      if ((st = serialize_absent(pre_ok))) return st;
-      std::vector<uint32_t> cl(n);
-      for (size_t s = 0; s < n; ++s) cl[s] = pre_ok[s] ? static_cast<uint32_t>(plen[s]) : 0;
-      std::vector<int64_t> pl(n);
-      if (sha_side) {
-        // decrypt_payload with the side stream's digests (ag_aon_decrypt_batch's key and
-        // length rules; the digests of the slices decrypted here hash the same lengths)
-        for (size_t s = 0; s < n; ++s) {
-          pl[s] = cl[s] < ag::kCipherKeyBytes ? -AG_RS_ERR_BAD_ENCODING
-                                              : static_cast<int64_t>(cl[s]) - ag::kCipherKeyBytes;
-          if (cl[s] < ag::kCipherKeyBytes) cl[s] = ag::kCipherKeyBytes;  // no-op
-        }
-        ag::BufferBatch bb;
-        if ((st = aon_batch(c, n, codewords, cw_stride, cl.data(), 0, &bb)) ||
-            (st = c->d_aon_keys.ensure(n * 16, c->stream)))
-          return st;
-        AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
-        if (ag::launch_derive_keys(bb, 1, c->d_aon_digests.as<uint8_t>(), c->d_aon_keys.as<uint8_t>(), c->stream) !=
-                hipSuccess ||
-            ag::launch_apply_keystream(bb, c->d_aon_keys.as<uint8_t>(), ag::kCipherKeyBytes, c->stream) != hipSuccess)
-          return AG_RS_ERR_DEVICE;
-        AG_HIP(hipStreamSynchronize(c->stream));
-      } else if ((st = ag_aon_decrypt_batch(c, k.aon, n, codewords, cw_stride, cl.data(), pl.data()))) {
-        return st;
-      }
-      for (size_t s = 0; s < n; ++s)
-        if (pre_ok[s]) plen[s] = pl[s];
-    }
-    // 6. SlicePayload::try_from on the (decrypted) payload
-    std::vector<uint8_t> sstat(n);
-    if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
-                                   parent_ids_out, data_offsets_out, data_lens_out)))
-      return st;
-    bool redo = false;
-    for (size_t s = 0; s < n; ++s) {
-      int32_t r = AG_RS_OK;
-      if (plen[s] < 0) {
-        r = -plen[s] == AG_RS_ERR_INVALID_PADDING ? AG_RS_ERR_BAD_ENCODING : static_cast<int32_t>(-plen[s]);
-      } else if (!h_same[s]) {
-        r = AG_RS_ERR_INVALID_MERKLE_TREE;
-      } else if (sstat[s] == AG_SLICE_TOO_LARGE) {
-        r = AG_RS_ERR_TOO_MUCH_DATA;
-      } else if (sstat[s] != AG_SLICE_OK) {
-        r = AG_RS_ERR_BAD_ENCODING;
-      }
-      status[s] = r;
-      ok[s] = r == AG_RS_OK;
-      slots_out[s] = ok[s] ? h_slot[s] : 0;
-      slice_indices_out[s] = ok[s] ? h_sidx[s] : 0;
-      is_last_out[s] = ok[s] ? h_last[s] : 0;
-      redo |= !ok[s] && __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
-    }
-    if (!redo) break;
-  }
-  // 7. fill_missing_shreds: every absent slot of a successful slice gets its datagram
-  if (k.aon < 0 && (st = serialize_absent(ok))) return st;
-  uint8_t* d_ok;
-  if ((st = pipe_buf(c, 20, n, &d_ok))) return st;
-  AG_HIP(hipMemcpyAsync(d_ok, ok.data(), n, hipMemcpyHostToDevice, c->stream));
-  if (ag::launch_pipe_merge_lens(reinterpret_cast<uint32_t*>(fresh), d_present, d_ok, n, packet_lens, c->stream) !=
-      hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  AG_HIP(hipStreamSynchronize(c->stream));
-  return AG_RS_OK;
-}
 
 // ---- mixed shred sizes (ag_rs_coder_*_batch_var; kernels in rs_var.hip) -------------------
 namespace {

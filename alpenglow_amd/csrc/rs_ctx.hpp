@@ -1,0 +1,335 @@
+// The device context behind the C ABI (include/alpenglow_rs.h) and the helpers the host
+// translation units share: rs_api.cpp (which defines them) and shredder_api.cpp.  Internal:
+// not installed, included only by the host .cpp files; nothing here is exported from the
+// shared object.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/alpenglow_rs.h"
+#include "cipher.hpp"
+#include "gf16.hpp"
+#include "rs_launch.hpp"
+
+#define AG_HIP(expr)                                  \
+  do {                                                \
+    if ((expr) != hipSuccess) return AG_RS_ERR_DEVICE; \
+  } while (0)
+
+namespace ag {
+namespace host __attribute__((visibility("hidden"))) {
+
+// Grow-only device buffer.
+struct DevBuf {
+  void* ptr = nullptr;
+  size_t size = 0;
+  int ensure(size_t n, hipStream_t stream) {
+    if (n <= size) return AG_RS_OK;
+    if (ptr) {
+      if (hipStreamSynchronize(stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+      (void)hipFree(ptr);
+      ptr = nullptr;
+      size = 0;
+    }
+    if (hipMalloc(&ptr, n) != hipSuccess) return AG_RS_ERR_OUT_OF_MEMORY;
+    size = n;
+    return AG_RS_OK;
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    size = 0;
+  }
+};
+
+// Grow-only pinned host buffer, mapped and coherent (fine-grained: never cached in the GPU's
+// L2, so one call's kernels cannot read another call's stale bytes): the crate-API
+// single-call kernels read and write it directly (zero-copy).
+struct PinBuf {
+  void* ptr = nullptr;
+  size_t size = 0;
+  int ensure(size_t n) {
+    if (n <= size) return AG_RS_OK;
+    release();
+    if (hipHostMalloc(&ptr, n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+      ptr = nullptr;
+      return AG_RS_ERR_OUT_OF_MEMORY;
+    }
+    if (hipHostGetDevicePointer(&dptr, ptr, 0) != hipSuccess) {
+      release();
+      return AG_RS_ERR_DEVICE;
+    }
+    size = n;
+    return AG_RS_OK;
+  }
+  template <typename T>
+  T* as() const {
+    return static_cast<T*>(ptr);
+  }
+  template <typename T>
+  T* dev() const {  // the same bytes as the device addresses them (zero-copy over PCIe)
+    return static_cast<T*>(dptr);
+  }
+  void* dptr = nullptr;
+  void release() {
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = dptr = nullptr;
+    size = 0;
+  }
+};
+
+}  // namespace host
+}  // namespace ag
+
+using ag::host::DevBuf;
+using ag::host::PinBuf;
+
+struct ag_rs_ctx {
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  bool tables_ready = false;
+  DevBuf d_exp, d_log, d_skew, d_log_walsh;
+  DevBuf scratch;                         // generic-kernel work rows
+  DevBuf d_flags, d_loc, d_blocks, d_mask;  // decode bookkeeping
+  DevBuf d_xmask, d_rows, d_xblocks;        // bitsliced general decode: masks, matrices
+  DevBuf d_x128, d_rows128;                 // W = 128 two-pass decode: masks, constants
+  uint64_t last_classes[16] = {};           // patterns per decoder class of the last decode call
+  int decode_depth = 0;                     // decode_device nesting (tail restrides decode inside)
+  uint32_t last_encode_kernels = 0;         // EncodeKernelBit of the last ag_rs_encode_batch / coder deshred batch
+  uint32_t last_window_kernels = 0;         // DecodeXKernelBit of the last coder deshred batch's window decode
+  DevBuf d_syn, d_synblocks;                // syndrome decoder: patterns, block ids
+  DevBuf d_corr, d_corrk, d_corrblocks;     // correction decoder: patterns, K picks, block ids
+  DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
+  DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
+  uint32_t last_merkle_kernels = 0;         // MerkleLeafKernelBit of the last Merkle build's leaf kernel
+  DevBuf d_leaf_sizes;                      // ag_merkle_build_batch_var: leaf size per slice
+  PinBuf h_leaf_sizes;                      // its pinned host staging
+  hipEvent_t leaf_sizes_ev = nullptr;       // recorded after its upload
+  DevBuf d_block_meta;                      // block trees: first[nblocks] (u64), then count[nblocks] (u32)
+  PinBuf h_block_meta;                      // its pinned host staging
+  hipEvent_t block_meta_ev = nullptr;       // recorded after its upload
+  DevBuf d_aon_lens, d_aon_digests, d_aon_keys;  // all-or-nothing transforms
+  DevBuf d_aon_lens2;                            // the side stream's SHA-256 lengths (AONT deshred)
+  hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
+  hipEvent_t side_fork = nullptr, side_join = nullptr;
+  DevBuf d_slice_meta;                           // slice framing / parsing metadata
+  DevBuf stage_pad, stage_mask;                  // restrided shards (sizes not whole 64-byte chunks)
+  DevBuf d_lens, d_strip;                   // coder batches: payload lengths, strip results
+  DevBuf d_reenc_mask;                      // uniform coder deshreds: the re-encode's store mask word
+  DevBuf d_pipe_few, d_pipe_mask;           // composed deshred: too-few flags, re-encode store masks
+  DevBuf d_present;                         // coder batches: per-slice present masks
+  PinBuf h_present;                         // their pinned host staging
+  hipEvent_t present_ev = nullptr;          // recorded after its upload
+  PinBuf h_lens;                            // coder shred batches: pinned staging of the lengths
+  hipEvent_t lens_ev = nullptr;             // recorded after its upload
+  PinBuf h_strip;                           // coder deshred batches: pinned staging of the results
+  PinBuf h_slice_meta;                      // slice parse batches: pinned staging of the results
+  PinBuf h_pipe_meta;                       // composed deshreds: pinned staging of the per-slice columns
+  DevBuf d_ed_base;                         // Ed25519 fixed-base table (ed25519.hpp)
+  static constexpr int kPipeBufs = 33;
+  DevBuf pipe[kPipeBufs];                   // composed shredder scratch (shredder_api.cpp's PipeBuf roles)
+  DevBuf d_sh_roots, d_sh_commit, d_sh_onvalid, d_sh_list;  // shred validation scratch
+  // host-memory calls: two staging slots, H2D / D2H streams next to the compute stream
+  struct Slot {
+    DevBuf in, out;
+    hipEvent_t up = nullptr, done = nullptr, down = nullptr;
+  } slot[2];
+  hipStream_t h2d = nullptr, d2h = nullptr;
+  DevBuf one_in, one_out;                 // crate-API single codeword
+  // per-call server (latency_server_kernel): mailbox in mapped host memory, its own stream
+  ag::LatencyMailbox* mb = nullptr;
+  ag::LatencyMailbox* mb_dev = nullptr;
+  hipStream_t server_stream = nullptr;
+  uint32_t server_seq = 0;
+  uint32_t server_p_seq = 0, server_dp_seq = 0;  // versions of the parameters last posted
+  bool server_broken = false;  // a job timed out: the server path is off for this context
+  bool fail_next_server_job = false;  // test aid: the next server job takes the timeout path
+  uint64_t server_jobs[4] = {};        // jobs posted per LatencyJob kind (test aid)
+  std::vector<PinBuf> abandoned_pins;  // staging a timed-out job named (freed once the server is gone)
+  std::vector<uint64_t> mask_host;        // last store-mask words uploaded to d_mask
+  std::vector<uint64_t> stage_mask_host;  // last restride masks uploaded to stage_mask
+  std::vector<uint64_t> xmask_host;       // last general-decode masks (d_xmask), W = xmask_w
+  size_t xmask_w = 0;
+  bool xmask_poly = false;                // d_rows holds polynomial-basis constants (per-lane)
+  std::vector<uint8_t> syn_key;             // (k, m, present flags) of the patterns in d_syn
+  std::vector<uint8_t> corr_key;            // (k, m, present flags) of the patterns in d_corr
+  std::vector<uint64_t> x128_host;          // last W = 128 masks uploaded to d_x128
+  std::vector<uint32_t> x128_ids;           // their per-block ids (d_xblocks)
+
+  int enter() { return hipSetDevice(device) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE; }
+
+  int ensure_tables() {
+    if (tables_ready) return AG_RS_OK;
+    const ag::Gf16Tables& t = ag::gf16_tables();
+    // log_walsh: Walsh-Hadamard transform (mod 65535) of the log table with log[0] := 0
+    // (crate engine/tables.rs initialize_log_walsh).
+    std::vector<uint16_t> lw(t.log, t.log + ag::kGfOrder);
+    lw[0] = 0;
+    for (size_t dist = 1; dist < ag::kGfOrder; dist <<= 1)
+      for (size_t r = 0; r < ag::kGfOrder; r += 2 * dist)
+        for (size_t i = r; i < r + dist; ++i) {
+          const uint32_t a = lw[i], b = lw[i + dist];
+          const uint32_t s = a + b, d = a - b;
+          lw[i] = static_cast<uint16_t>(s + (s >> 16));
+          lw[i + dist] = static_cast<uint16_t>(d + (d >> 16));
+        }
+    int st;
+    if ((st = d_exp.ensure(sizeof t.exp, stream)) || (st = d_log.ensure(sizeof t.log, stream)) ||
+        (st = d_skew.ensure(sizeof t.skew, stream)) || (st = d_log_walsh.ensure(lw.size() * 2, stream)))
+      return st;
+    AG_HIP(hipMemcpy(d_exp.ptr, t.exp, sizeof t.exp, hipMemcpyHostToDevice));
+    AG_HIP(hipMemcpy(d_log.ptr, t.log, sizeof t.log, hipMemcpyHostToDevice));
+    AG_HIP(hipMemcpy(d_skew.ptr, t.skew, sizeof t.skew, hipMemcpyHostToDevice));
+    AG_HIP(hipMemcpy(d_log_walsh.ptr, lw.data(), lw.size() * 2, hipMemcpyHostToDevice));
+    tables_ready = true;
+    return AG_RS_OK;
+  }
+
+  ag::GfDeviceTables dtables() const {
+    return {d_exp.as<uint16_t>(), d_log.as<uint16_t>(), d_skew.as<uint16_t>(), d_log_walsh.as<uint16_t>()};
+  }
+
+  int ensure_side_stream() {
+    if (side) return AG_RS_OK;
+    AG_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    AG_HIP(hipEventCreateWithFlags(&side_fork, hipEventDisableTiming));
+    AG_HIP(hipEventCreateWithFlags(&side_join, hipEventDisableTiming));
+    return AG_RS_OK;
+  }
+
+  int ensure_copy_streams() {
+    if (h2d) return AG_RS_OK;
+    AG_HIP(hipStreamCreateWithFlags(&h2d, hipStreamNonBlocking));
+    AG_HIP(hipStreamCreateWithFlags(&d2h, hipStreamNonBlocking));
+    for (Slot& s : slot) {
+      AG_HIP(hipEventCreateWithFlags(&s.up, hipEventDisableTiming));
+      AG_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+      AG_HIP(hipEventCreateWithFlags(&s.down, hipEventDisableTiming));
+      AG_HIP(hipEventRecord(s.down, d2h));  // slots start free
+    }
+    return AG_RS_OK;
+  }
+
+  void server_stop() {
+    if (!mb) return;
+    (void)hipSetDevice(device);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0) {
+      mb->kind = ag::kJobQuit;
+      __atomic_store_n(&mb->doorbell, ++server_seq, __ATOMIC_RELEASE);
+      while (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0 &&
+             std::chrono::steady_clock::now() - t0 < std::chrono::seconds(2)) {
+      }
+    }
+    if (__atomic_load_n(&mb->alive, __ATOMIC_ACQUIRE) != 0) {
+      // a server that neither served nor quit (server_broken): waiting on its stream could
+      // block forever, and it may still write the mailbox or an abandoned staging buffer,
+      // so those stay allocated
+      mb = mb_dev = nullptr;
+      server_stream = nullptr;
+      abandoned_pins.clear();
+      return;
+    }
+    (void)hipStreamSynchronize(server_stream);  // the server has exited (quit or idle timeout)
+    for (PinBuf& b : abandoned_pins) b.release();
+    abandoned_pins.clear();
+    (void)hipStreamDestroy(server_stream);
+    (void)hipHostFree(mb);
+    mb = mb_dev = nullptr;
+    server_stream = nullptr;
+  }
+
+  ~ag_rs_ctx() {
+    server_stop();
+    if (side) {
+      (void)hipSetDevice(device);
+      (void)hipStreamSynchronize(side);
+      (void)hipEventDestroy(side_fork);
+      (void)hipEventDestroy(side_join);
+      (void)hipStreamDestroy(side);
+    }
+    if (own_stream) {
+      (void)hipSetDevice(device);
+      (void)hipStreamSynchronize(own_stream);
+    }
+    if (h2d) {
+      (void)hipStreamSynchronize(h2d);
+      (void)hipStreamSynchronize(d2h);
+      for (Slot& s : slot) {
+        s.in.release();
+        s.out.release();
+        for (hipEvent_t e : {s.up, s.done, s.down})
+          if (e) (void)hipEventDestroy(e);
+      }
+      (void)hipStreamDestroy(h2d);
+      (void)hipStreamDestroy(d2h);
+    }
+    for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &d_mask,
+                      &d_xmask, &d_rows, &d_xblocks, &d_x128, &d_rows128, &d_syn, &d_synblocks, &d_corr, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_pad, &stage_mask, &d_slice_meta, &one_in,
+                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta, &d_leaf_sizes})
+      b->release();
+    for (DevBuf& b : pipe) b.release();
+    if (present_ev) {
+      (void)hipEventSynchronize(present_ev);
+      (void)hipEventDestroy(present_ev);
+    }
+    h_present.release();
+    if (lens_ev) {
+      (void)hipEventSynchronize(lens_ev);
+      (void)hipEventDestroy(lens_ev);
+    }
+    h_lens.release();
+    if (block_meta_ev) {
+      (void)hipEventSynchronize(block_meta_ev);
+      (void)hipEventDestroy(block_meta_ev);
+    }
+    h_block_meta.release();
+    if (leaf_sizes_ev) {
+      (void)hipEventSynchronize(leaf_sizes_ev);
+      (void)hipEventDestroy(leaf_sizes_ev);
+    }
+    h_leaf_sizes.release();
+    h_strip.release();
+    h_slice_meta.release();
+    h_pipe_meta.release();
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+};
+
+// The helpers the composed shredders (shredder_api.cpp) call in rs_api.cpp, where each is
+// defined and documented.
+namespace ag {
+namespace host __attribute__((visibility("hidden"))) {
+
+constexpr size_t kDataShreds = AG_RS_DATA_SHREDS;
+constexpr size_t kMaxPayload = kDataShreds * AG_RS_MAX_DATA_PER_SHRED - 1;
+
+int ensure_empty_roots(ag_rs_ctx* c);
+int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
+                      size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
+                      size_t proofs_stride);
+int aon_batch(ag_rs_ctx* c, size_t n, uint8_t* buffers, size_t stride, const uint32_t* lens, uint32_t extra,
+              ag::BufferBatch* bb);
+int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data_stride, size_t data_bytes,
+                        const uint32_t* shred_index, const uint8_t* proofs, size_t proofs_stride, size_t height,
+                        const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
+                        const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
+                        const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
+                        uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes = nullptr,
+                        size_t leaf_nodes_stride = 0, uint32_t leaves_per_tree = 0, size_t group_stride = 0,
+                        uint32_t skip_row = 0, bool roots_ready = false);
+int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                       int64_t* plen, size_t m, bool no_surplus = false);
+bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);
+
+}  // namespace host
+}  // namespace ag

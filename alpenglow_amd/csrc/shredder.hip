@@ -6,7 +6,7 @@
 // fill_missing_shreds :576-611), plus the receiver's per-shred checks
 // (ValidatedShred::try_new with the blockstore's cached commitment,
 // validated_shred.rs:52-81).  The stages themselves (framing, RS, Merkle, Ed25519, wire) are
-// the library's other kernels; ag_shredder_*_batch in rs_api.cpp chains them.
+// the library's other kernels; ag_shredder_*_batch in shredder_api.cpp chains them.
 #include <hip/hip_runtime.h>
 
 #include "shredder.hpp"

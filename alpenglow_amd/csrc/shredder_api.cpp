@@ -1,0 +1,962 @@
+// Host side of the composed shredders: ag_shredder_shred_batch[_var|_kind] and
+// ag_shredder_deshred_batch[_kind] (include/alpenglow_rs.h), the four shredders of shredder.rs
+// (Regular, CodingOnly, PETS, AONT) chained on the device from the batched stages of rs_api.cpp
+// (slice framing, ReedSolomonCoder, Merkle trees, signatures, all-or-nothing transforms) and
+// the glue kernels of shredder.hip / wire.hip.
+//
+// The entry points keep what is their own (argument checks, framing, the coder call, how a
+// failed slice is decoded again) and share the stages around it: the row layout as data
+// (ShredderKind), shred_tail, deshred_front, pipe_statuses, fill_missing.  Side-stream rule:
+// every error return between recording side_fork and waiting on side_join drains c->side first
+// (drain_side), so a failed call never leaves work running on buffers its caller gets back.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "../../include/alpenglow_rs.h"
+#include "cipher.hpp"
+#include "ed25519.hpp"
+#include "merkle.hpp"
+#include "rs_ctx.hpp"
+#include "rs_launch.hpp"
+#include "shredder.hpp"
+#include "wire.hpp"
+
+using namespace ag::host;
+
+namespace {
+
+constexpr size_t kPipeProofBytes = 32 * ag::kPipeHeight;  // one Merkle path of a slice tree
+
+// The roles of the composed shredders' scratch (ag_rs_ctx::pipe): one grow-only buffer per role,
+// shared by every entry point of a context (calls on a context are ordered on its stream).  The
+// shred side uses the per-shred columns it writes and the two per-slice buffers at the end.
+// No two roles share a buffer.  One role has two users in the Regular deshred: kBufMerkleList
+// is the compaction list of the proof verify (side stream) and then of the Merkle rebuild (main
+// stream) -- safe because the main stream waits on side_join before the second validation, long
+// before the rebuild is enqueued.
+enum PipeBuf : int {
+  // per shred (N = 64 n rows): the ShredColumns of both sides
+  kBufKind,
+  kBufSlot,
+  kBufSliceIndex,
+  kBufIsLast,
+  kBufShredIndex,
+  kBufDataLen,
+  kBufSig,
+  kBufProof,
+  kBufHeight,
+  // per shred, deshred side
+  kBufWire,        // deserialize status
+  kBufValStatus,   // the full validation's status
+  kBufRoots,       // every plausible shred's derived root
+  kBufPlausible,   // the datagram parsed and fits its slot
+  kBufMerkleList,  // 4 (N + 1): list scratch of the Merkle kernels
+  kBufLeafFlags,   // Regular: leaves the rebuild hashes again
+  kBufFreshLens,   // 4 N: lengths of the datagrams fill_missing serialized
+  // per slice, deshred side: the picked shred (pipe_pick) and its validation
+  kBufPick,
+  kBufPickData,
+  kBufPickProof,
+  kBufPickSlot,
+  kBufPickSliceIndex,
+  kBufPickIsLast,
+  kBufPickShredIndex,
+  kBufPickSig,
+  kBufPickStatus,
+  kBufCommits,
+  kBufHasCached,
+  kBufPerSlice,     // pipe_check's outputs and the rebuilt roots (carved up by deshred_front)
+  kBufCoderWords,   // CodingOnly / PETS: the kept shreds as codeword-row present words
+  kBufSame,         // rebuilt root == signed root
+  kBufSliceOk,      // the slices fill_missing serves
+  // per slice, shred side (callers that pass no roots_out / sigs_out)
+  kBufSliceRoots,
+  kBufSliceSigs,
+  kPipeBufCount
+};
+static_assert(kPipeBufCount == ag_rs_ctx::kPipeBufs);
+
+int pipe_buf(ag_rs_ctx* c, PipeBuf i, size_t bytes, uint8_t** out) {
+  const int st = c->pipe[i].ensure(std::max<size_t>(bytes, 64), c->stream);
+  if (st) return st;
+  *out = c->pipe[i].as<uint8_t>();
+  return AG_RS_OK;
+}
+
+// The side-stream rule's error return: wait for what the side stream still runs, then fail.
+int drain_side(ag_rs_ctx* c, int st) {
+  if (c->side) (void)hipStreamSynchronize(c->side);
+  return st;
+}
+
+// The per-slice columns pipe_check writes (present | slot | slice index | is_last, contiguous
+// from `present`) read back in one copy into pinned staging: views valid until the next call
+// on the context
+struct PipeMeta {
+  const uint64_t *present, *slot, *sidx;
+  const uint8_t* last;
+};
+int read_pipe_meta(ag_rs_ctx* c, const uint64_t* d_present, size_t n, PipeMeta* m) {
+  const int st = c->h_pipe_meta.ensure(25 * n);
+  if (st) return st;
+  uint8_t* h = c->h_pipe_meta.as<uint8_t>();
+  AG_HIP(hipMemcpyAsync(h, d_present, 25 * n, hipMemcpyDeviceToHost, c->stream));
+  AG_HIP(hipStreamSynchronize(c->stream));
+  m->present = reinterpret_cast<const uint64_t*>(h);
+  m->slot = m->present + n;
+  m->sidx = m->slot + n;
+  m->last = h + 24 * n;
+  return AG_RS_OK;
+}
+
+bool pipe_args_ok(size_t nslices, size_t S, const uint8_t* codewords, const uint8_t* packets,
+                  const uint32_t* packet_lens) {
+  return S != 0 && S % 2 == 0 && S <= 1024 && nslices < (size_t{1} << 24) &&
+         (nslices == 0 || (codewords && packets && packet_lens)) && reinterpret_cast<uintptr_t>(codewords) % 16 == 0;
+}
+
+// Output shred j of a slice <-> codeword row (data rows 0..31, coding rows 32..32+m-1):
+// Regular / AONT: j; CodingOnly: 32 + j (the 64 coding shreds, no data shreds: shredder.rs:
+// 367-376); PETS: j for j < 31, j + 1 after (the data shred holding the key withheld,
+// :414-422).  The pipeline addresses the output rows in the caller's codeword buffer itself
+// (grouped_row_offset: base row row0, slice stride cw_stride, row `skip` and later one shard
+// further), so no row is copied between the coder's layout and the datagrams'.
+struct ShredderKind {
+  uint32_t m;         // coding shreds of the coder (ReedSolomonCoder::new(CODING_OUTPUT_SHREDS))
+  uint32_t num_data;  // DATA_OUTPUT_SHREDS
+  int aon;            // AG_AON_* or -1
+  uint32_t row0;      // codeword row of output shred 0
+  uint32_t skip;      // output shreds >= skip sit one row further (0: none)
+  // the kernels' group stride: rows addressed per slice (the slice stride), or 0 for flat
+  // addressing, row 64 s + j of the whole buffer (Regular: its slices are exactly 64 rows)
+  size_t group_stride;
+};
+bool shredder_kind(int kind, size_t cw_stride, ShredderKind* k) {
+  switch (kind) {
+    case AG_SHREDDER_REGULAR: *k = {32, 32, -1, 0, 0, 0}; return true;
+    case AG_SHREDDER_CODING_ONLY: *k = {64, 0, -1, kDataShreds, 0, cw_stride}; return true;
+    case AG_SHREDDER_PETS: *k = {33, 31, AG_AON_PETS, 0, 31, cw_stride}; return true;
+    case AG_SHREDDER_AONT: *k = {32, 32, AG_AON_AONT, 0, 0, cw_stride}; return true;
+    default: return false;
+  }
+}
+uint32_t kind_row(const ShredderKind& k, uint32_t j) { return k.row0 + j + (k.skip && j >= k.skip ? 1u : 0u); }
+// the kept output shreds of one slice (present bit j) as ag_rs_coder_deshred_batch's flags of its
+// data rows (dp[32]) and coding rows (cp[m]); rows that are no output shred keep their flag
+void coder_flags(const ShredderKind& k, uint64_t present, uint8_t* dp, uint8_t* cp) {
+  for (uint32_t j = 0; j < ag::kPipeShreds; ++j) {
+    const uint32_t r = kind_row(k, j);
+    const uint8_t bit = static_cast<uint8_t>((present >> j) & 1);
+    if (r < kDataShreds) dp[r] = bit;
+    else cp[r - kDataShreds] = bit;
+  }
+}
+// the Merkle tree over the 64 output rows of each slice: roots, proofs (nodes in context scratch)
+int kind_merkle(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint8_t* codewords, size_t cw_stride,
+                uint8_t* roots, uint8_t* proofs) {
+  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
+  int st;
+  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream)) || (st = ensure_empty_roots(c))) return st;
+  ag::MerkleBuildParams mb{};
+  mb.leaves = codewords + k.row0 * S;
+  mb.leaf_stride = S;
+  mb.slice_stride = cw_stride;
+  mb.skip_leaf = k.skip;
+  mb.leaf_bytes = static_cast<uint32_t>(S);
+  mb.n_leaves = ag::kPipeShreds;
+  mb.nslices = n;
+  mb.empty_roots = c->d_empty_roots.as<uint32_t>();
+  mb.roots = roots;
+  mb.proofs = proofs;
+  mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
+  c->last_merkle_kernels = 0;
+  return ag::launch_merkle_build(mb, c->d_merkle_nodes.as<uint8_t>(), nodes_stride, c->stream,
+                                 &c->last_merkle_kernels) == hipSuccess
+             ? AG_RS_OK
+             : AG_RS_ERR_DEVICE;
+}
+
+// ag_slice_sign_batch on the context's side stream, forked from the main stream's current point
+// (the roots): the signing (one signature per lane, latency-bound) overlaps the serialization of
+// everything else in the datagrams; the caller waits on side_join before it patches the
+// signatures in.
+int sign_on_side(ag_rs_ctx* c, size_t n, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
+                 const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs) {
+  int st;
+  if ((st = c->ensure_side_stream())) return st;
+  AG_HIP(hipEventRecord(c->side_fork, c->stream));
+  if (hipStreamWaitEvent(c->side, c->side_fork, 0) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
+  std::swap(c->stream, c->side);
+  st = ag_slice_sign_batch(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs, nullptr);
+  std::swap(c->stream, c->side);
+  if (st) return drain_side(c, st);
+  if (hipEventRecord(c->side_join, c->side) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
+  return AG_RS_OK;
+}
+
+// The shred side from the encoded codewords on: the slice Merkle trees (roots and every shred's
+// path), slice_sig = sign(SliceCommitment(header, root)) on the side stream while the main
+// stream serializes the 64 datagrams per slice (header and signature shared by the slice's
+// rows), then the signatures patched in.  roots_out / sigs_out null: context scratch.
+// d_sizes (device, nullable): one shred size per slice -- the var Merkle build, rows packed at
+// the slice's own size (S is 0 then); null: shreds of S bytes in the rows of `k`.
+// nblocks > 0: the block hashes over the roots, a chain of dependent levels a few workgroups
+// wide, placed where the main stream would otherwise only wait for the signatures.
+int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint32_t* d_sizes, uint8_t* codewords,
+               size_t cw_stride, const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
+               const uint8_t* seed, const uint8_t* pk, uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets,
+               size_t packet_stride, uint32_t* packet_lens, size_t nblocks, const uint32_t* block_counts,
+               uint8_t* block_hashes_out) {
+  const size_t N = n * ag::kPipeShreds;
+  int st;
+  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kind, *sidx, *dlen, *height;
+  if (!roots && (st = pipe_buf(c, kBufSliceRoots, 32 * n, &roots))) return st;
+  if (!sigs && (st = pipe_buf(c, kBufSliceSigs, 64 * n, &sigs))) return st;
+  if ((st = pipe_buf(c, kBufProof, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, kBufKind, N, &kind)) ||
+      (st = pipe_buf(c, kBufShredIndex, 4 * N, &sidx)) || (st = pipe_buf(c, kBufDataLen, 4 * N, &dlen)) ||
+      (st = pipe_buf(c, kBufHeight, 4 * N, &height)))
+    return st;
+  if (reinterpret_cast<uintptr_t>(roots) % 16) return AG_RS_ERR_INVALID_ARGUMENT;  // (the Merkle build's stores)
+  if ((st = d_sizes ? merkle_var_launch(c, n, d_sizes, codewords, cw_stride, roots, nullptr, 0, proofs,
+                                        ag::kPipeShreds * kPipeProofBytes)
+                    : kind_merkle(c, k, n, S, codewords, cw_stride, roots, proofs)))
+    return st;
+  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
+  ag::PipeExpandParams ep{};
+  ep.nslices = n;
+  ep.shred_bytes = static_cast<uint32_t>(S);
+  ep.num_data = k.num_data;
+  ep.kind = kind;
+  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
+  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
+  ep.height = reinterpret_cast<uint32_t*>(height);
+  ep.slice_bytes = d_sizes;
+  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
+  ag::ShredColumns cols{};
+  cols.kind = kind;
+  cols.slot = const_cast<uint64_t*>(slots);
+  cols.slice_index = const_cast<uint64_t*>(slice_indices);
+  cols.is_last = const_cast<uint8_t*>(is_last);
+  cols.shred_index = ep.shred_index;
+  cols.data = codewords + k.row0 * S;
+  cols.data_stride = d_sizes ? AG_RS_MAX_DATA_PER_SHRED : S;
+  cols.group_stride = k.group_stride;
+  cols.skip_row = k.skip;
+  cols.row_sizes = d_sizes;
+  cols.data_len = ep.data_len;
+  cols.sig = sigs;
+  cols.proof = proofs;
+  cols.proof_stride = kPipeProofBytes;
+  cols.height = ep.height;
+  cols.hdr_group = ag::kPipeShreds;
+  cols.skip_sig = 1;
+  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
+    return drain_side(c, AG_RS_ERR_DEVICE);
+  if (nblocks && (st = ag_block_tree_batch(c, nblocks, block_counts, roots, block_hashes_out, nullptr, 0, nullptr, 0)))
+    return drain_side(c, st);
+  if (hipStreamWaitEvent(c->stream, c->side_join, 0) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
+  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  return AG_RS_OK;
+}
+
+// What steps 1-3 of a deshred leave for the later ones: the per-shred columns (payload rows
+// parsed straight into their codeword rows) and, per slice, pipe_check's outputs on the device
+// and (PipeMeta) on the host.
+struct DeshredViews {
+  ag::ShredColumns cols;
+  uint8_t* wire;        // [N] deserialize status
+  uint8_t* sroot;       // [n][32] the kept shreds' signed root
+  uint8_t* roots2;      // [n][32] for the rebuilt tree's root
+  uint8_t* ssig;        // [n][64]
+  uint64_t* d_present;  // [n] the shreds kept
+  uint64_t* d_slot;
+  uint8_t *ssidx, *slast;
+  PipeMeta h;           // present | slot | slice index | is_last on the host
+};
+
+// Steps 1-3 of a deshred in the row layout `k`:
+// 1. network::deserialize (absent slots have length 0: malformed, never written);
+// 2. ValidatedShred::try_new: one signature per slice (its first plausible shred), then every
+//    shred against its slice's commitment (the blockstore's cached commitment; signature only
+//    without a cache);
+// 3. per slice: the shreds kept, the root, header and signature, read back to the host.
+// Every plausible shred's root (derive_root) is computed on the side stream: it needs only the
+// parse and the pick's plausibility flags, so it overlaps the picked shreds' signature checks
+// (one signature per lane: a latency-bound kernel).  leaf_nodes (nullable; with its stride and
+// leaves_per_tree): that verify also keeps each shred's leaf digest there, at (slice, index),
+// for a Merkle rebuild's level 0.
+int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint8_t* packets,
+                  size_t packet_stride, const uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords,
+                  uint8_t* leaf_nodes, size_t leaf_nodes_stride, uint32_t leaves_per_tree, DeshredViews* v) {
+  const size_t N = n * ag::kPipeShreds;
+  int st;
+  uint8_t *kind, *slot, *sidx, *last, *shidx, *dlen, *sig, *proof, *height, *wire, *vstat, *roots;
+  if ((st = pipe_buf(c, kBufKind, N, &kind)) || (st = pipe_buf(c, kBufSlot, 8 * N, &slot)) ||
+      (st = pipe_buf(c, kBufSliceIndex, 8 * N, &sidx)) || (st = pipe_buf(c, kBufIsLast, N, &last)) ||
+      (st = pipe_buf(c, kBufShredIndex, 4 * N, &shidx)) || (st = pipe_buf(c, kBufDataLen, 4 * N, &dlen)) ||
+      (st = pipe_buf(c, kBufSig, 64 * N, &sig)) || (st = pipe_buf(c, kBufProof, kPipeProofBytes * N, &proof)) ||
+      (st = pipe_buf(c, kBufHeight, 4 * N, &height)) || (st = pipe_buf(c, kBufWire, N, &wire)) ||
+      (st = pipe_buf(c, kBufValStatus, N, &vstat)) || (st = pipe_buf(c, kBufRoots, 32 * N, &roots)))
+    return st;
+  uint8_t *pick, *gdata, *gproof, *gslot, *gsidx, *glast, *gidx, *gsig, *pstat, *commits, *hasc;
+  if ((st = pipe_buf(c, kBufPick, n, &pick)) || (st = pipe_buf(c, kBufPickData, n * S, &gdata)) ||
+      (st = pipe_buf(c, kBufPickProof, kPipeProofBytes * n, &gproof)) ||
+      (st = pipe_buf(c, kBufPickSlot, 8 * n, &gslot)) || (st = pipe_buf(c, kBufPickSliceIndex, 8 * n, &gsidx)) ||
+      (st = pipe_buf(c, kBufPickIsLast, n, &glast)) || (st = pipe_buf(c, kBufPickShredIndex, 4 * n, &gidx)) ||
+      (st = pipe_buf(c, kBufPickSig, 64 * n, &gsig)) || (st = pipe_buf(c, kBufPickStatus, n, &pstat)) ||
+      (st = pipe_buf(c, kBufCommits, ag::kSliceCommitmentLen * n, &commits)) ||
+      (st = pipe_buf(c, kBufHasCached, n, &hasc)))
+    return st;
+  uint8_t *plaus, *dlist, *per_slice;
+  if ((st = pipe_buf(c, kBufPlausible, N, &plaus)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &dlist)) ||
+      (st = pipe_buf(c, kBufPerSlice, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice)) ||
+      (st = c->ensure_side_stream()))
+    return st;
+  ag::ShredColumns& cols = v->cols;
+  cols = ag::ShredColumns{};
+  cols.kind = kind;
+  cols.slot = reinterpret_cast<uint64_t*>(slot);
+  cols.slice_index = reinterpret_cast<uint64_t*>(sidx);
+  cols.is_last = last;
+  cols.shred_index = reinterpret_cast<uint32_t*>(shidx);
+  cols.data = codewords + k.row0 * S;
+  cols.data_stride = S;
+  cols.group_stride = k.group_stride;
+  cols.skip_row = k.skip;
+  cols.data_len = reinterpret_cast<uint32_t*>(dlen);
+  cols.sig = sig;
+  cols.proof = proof;
+  cols.proof_stride = kPipeProofBytes;
+  cols.height = reinterpret_cast<uint32_t*>(height);
+  v->wire = wire;
+  if (ag::launch_shred_deserialize(packets, packet_stride, packet_lens, N, cols, wire, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  ag::PipePickParams pp{};
+  pp.nslices = n;
+  pp.shred_bytes = static_cast<uint32_t>(S);
+  pp.num_data = k.num_data;
+  pp.wire_status = wire;
+  pp.cols = cols;
+  pp.pick = pick;
+  pp.g_data = gdata;
+  pp.g_proof = gproof;
+  pp.g_slot = reinterpret_cast<uint64_t*>(gslot);
+  pp.g_slice_index = reinterpret_cast<uint64_t*>(gsidx);
+  pp.g_is_last = glast;
+  pp.g_shred_index = reinterpret_cast<uint32_t*>(gidx);
+  pp.g_sig = gsig;
+  pp.plausible = plaus;  // per shred: the datagram parsed and fits its slot
+  AG_HIP(hipMemsetAsync(gdata, 0, n * S, c->stream));  // slices without a pick: defined bytes
+  AG_HIP(hipMemsetAsync(gidx, 0, 4 * n, c->stream));
+  if (ag::launch_pipe_pick(pp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  ag::MerkleVerifyParams mp{};
+  mp.leaves = cols.data;
+  mp.leaf_stride = S;
+  mp.leaf_bytes = static_cast<uint32_t>(S);
+  mp.height = ag::kPipeHeight;
+  mp.index = cols.shred_index;
+  mp.proofs = proof;
+  mp.proofs_stride = kPipeProofBytes;
+  mp.n = N;
+  mp.roots_out = roots;
+  mp.active = plaus;
+  mp.list = reinterpret_cast<uint32_t*>(dlist);
+  mp.leaf_nodes = leaf_nodes;
+  mp.leaf_nodes_stride = leaf_nodes_stride;
+  mp.leaves_per_tree = leaves_per_tree;
+  mp.group_stride = k.group_stride;
+  mp.skip_row = k.skip;
+  AG_HIP(hipEventRecord(c->side_fork, c->stream));
+  if (hipStreamWaitEvent(c->side, c->side_fork, 0) != hipSuccess ||
+      ag::launch_merkle_verify(mp, c->side) != hipSuccess || hipEventRecord(c->side_join, c->side) != hipSuccess)
+    return drain_side(c, AG_RS_ERR_DEVICE);
+  if ((st = shred_validate_impl(c, n, gdata, S, S, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
+                                pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, nullptr, pstat,
+                                nullptr, commits)))
+    return drain_side(c, st);
+  if (ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream) != hipSuccess ||
+      hipStreamWaitEvent(c->stream, c->side_join, 0) != hipSuccess)
+    return drain_side(c, AG_RS_ERR_DEVICE);
+  if ((st = shred_validate_impl(c, N, cols.data, S, S, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
+                                cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds, plaus,
+                                vstat, roots, nullptr, leaf_nodes, leaf_nodes_stride, leaves_per_tree, k.group_stride,
+                                k.skip, true)))
+    return st;
+  // 32-byte rows first: the Merkle build wants 16-byte aligned roots
+  v->sroot = per_slice;
+  v->roots2 = v->sroot + 32 * n;
+  v->ssig = v->roots2 + 32 * n;
+  v->d_present = reinterpret_cast<uint64_t*>(v->ssig + 64 * n);
+  v->d_slot = v->d_present + n;
+  v->ssidx = reinterpret_cast<uint8_t*>(v->d_slot + n);
+  v->slast = v->ssidx + 8 * n;
+  ag::PipeCheckParams kp{};
+  kp.nslices = n;
+  kp.shred_bytes = static_cast<uint32_t>(S);
+  kp.num_data = k.num_data;
+  kp.wire_status = wire;
+  kp.val_status = vstat;
+  kp.roots = roots;
+  kp.cols = cols;
+  kp.present = v->d_present;
+  kp.root = v->sroot;
+  kp.slot = v->d_slot;
+  kp.slice_index = reinterpret_cast<uint64_t*>(v->ssidx);
+  kp.is_last = v->slast;
+  kp.sig = v->ssig;
+  if (ag::launch_pipe_check(kp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  return read_pipe_meta(c, v->d_present, n, &v->h);
+}
+
+// Shredder::deshred's result per slice from the coder's (plen: payload length or -error), the
+// Merkle check's (h_same) and SlicePayload::try_from's (sstat): status, ok, and the slice's
+// header for the slices that succeeded (zero for the others).
+void pipe_statuses(size_t n, const int64_t* plen, const uint8_t* h_same, const uint8_t* sstat, const PipeMeta& h,
+                   int32_t* status, uint8_t* ok, uint64_t* slots_out, uint64_t* slice_indices_out,
+                   uint8_t* is_last_out) {
+  for (size_t s = 0; s < n; ++s) {
+    int32_t r = AG_RS_OK;
+    if (plen[s] < 0) {
+      r = -plen[s] == AG_RS_ERR_INVALID_PADDING ? AG_RS_ERR_BAD_ENCODING : static_cast<int32_t>(-plen[s]);
+    } else if (!h_same[s]) {
+      r = AG_RS_ERR_INVALID_MERKLE_TREE;
+    } else if (sstat[s] == AG_SLICE_TOO_LARGE) {
+      r = AG_RS_ERR_TOO_MUCH_DATA;
+    } else if (sstat[s] != AG_SLICE_OK) {
+      r = AG_RS_ERR_BAD_ENCODING;
+    }
+    status[s] = r;
+    ok[s] = r == AG_RS_OK;
+    slots_out[s] = ok[s] ? h.slot[s] : 0;
+    slice_indices_out[s] = ok[s] ? h.sidx[s] : 0;
+    is_last_out[s] = ok[s] ? h.last[s] : 0;
+  }
+}
+
+// fill_missing_shreds: the datagrams of the absent slots of the slices with ok[s], serialized
+// into their packets; their lengths go to *fresh (pipe_merge_lens moves the final slices'
+// lengths into packet_lens), the uploaded flags to *d_ok.  Enqueued only: `ok` is host memory
+// the upload reads, so the caller synchronizes before it changes.
+int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const DeshredViews& v, const uint8_t* ok,
+                 uint8_t* packets, size_t packet_stride, uint8_t** d_ok, uint32_t** fresh) {
+  const size_t N = n * ag::kPipeShreds;
+  int st;
+  uint8_t* fl;
+  if ((st = pipe_buf(c, kBufSliceOk, n, d_ok)) || (st = pipe_buf(c, kBufFreshLens, 4 * N, &fl))) return st;
+  *fresh = reinterpret_cast<uint32_t*>(fl);
+  AG_HIP(hipMemcpyAsync(*d_ok, ok, n, hipMemcpyHostToDevice, c->stream));
+  ag::PipeExpandParams ep{};
+  ep.nslices = n;
+  ep.shred_bytes = static_cast<uint32_t>(S);
+  ep.num_data = k.num_data;
+  ep.skip = v.d_present;
+  ep.slice_ok = *d_ok;
+  ep.kind = v.cols.kind;
+  ep.shred_index = v.cols.shred_index;
+  ep.data_len = v.cols.data_len;
+  ep.height = v.cols.height;
+  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  ag::ShredColumns fc = v.cols;
+  fc.slot = v.d_slot;
+  fc.slice_index = reinterpret_cast<uint64_t*>(v.ssidx);
+  fc.is_last = v.slast;
+  fc.sig = v.ssig;
+  fc.hdr_group = ag::kPipeShreds;
+  if (ag::launch_shred_serialize(fc, N, packets, packet_stride, *fresh, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  return AG_RS_OK;
+}
+
+// Step 6b of ag_shredder_deshred_batch for slice s: its datagram rows are parsed again into
+// the codeword (the pass before rewrote the restored and re-encoded rows), the kept shreds
+// (present bit mask) go through ReedSolomonCoder::deshred with the crate's EXACT decoder,
+// and the Merkle rebuild (roots2 row s, the slice's proof rows), root comparison and
+// SlicePayload parse are redone for this slice.  Outputs replace slice s's entries.
+int pipe_rerun_exact(ag_rs_ctx* c, const ShredderKind& k, size_t s, size_t S, const uint8_t* packets,
+                     size_t packet_stride, const uint32_t* packet_lens, const DeshredViews& v, uint8_t* codewords,
+                     uint8_t* same, int64_t* plen, uint8_t* h_same, uint8_t* sstat, uint8_t* parent_flag,
+                     uint8_t* parent_id, uint32_t* data_offset, uint32_t* data_len) {
+  constexpr size_t kRows = ag::kPipeShreds;
+  const size_t r0 = s * kRows, cw_stride = kRows * S;
+  uint8_t* cw = codewords + s * cw_stride;
+  ag::ShredColumns rc = v.cols;
+  rc.kind += r0;
+  rc.slot += r0;
+  rc.slice_index += r0;
+  rc.is_last += r0;
+  rc.shred_index += r0;
+  rc.data = cw;
+  rc.data_len += r0;
+  rc.sig += 64 * r0;
+  rc.proof += r0 * v.cols.proof_stride;
+  rc.height += r0;
+  if (ag::launch_shred_deserialize(packets + r0 * packet_stride, packet_stride, packet_lens + r0, kRows, rc,
+                                   v.wire + r0, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  uint8_t dp[ag::kPipeData], cp[kRows - ag::kPipeData];
+  coder_flags(k, v.h.present[s], dp, cp);
+  int st = ag_rs_coder_deshred_batch(c, kRows - ag::kPipeData, 1, S, cw, cw_stride, dp, cp, AG_RS_DECODE_EXACT, plen);
+  if (st) return st;
+  *h_same = 0;
+  if (*plen < 0) return AG_RS_OK;
+  if ((st = ag_merkle_build_batch(c, kRows, S, 1, cw, S, cw_stride, v.roots2 + 32 * s, nullptr, 0,
+                                  v.cols.proof + r0 * v.cols.proof_stride, kRows * v.cols.proof_stride)))
+    return st;
+  if (ag::launch_pipe_root_cmp(v.roots2 + 32 * s, v.sroot + 32 * s, 1, same + s, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  AG_HIP(hipMemcpyAsync(h_same, same + s, 1, hipMemcpyDeviceToHost, c->stream));
+  // synchronous: h_same has landed when it returns
+  return ag_slice_parse_batch(c, 1, cw, cw_stride, plen, sstat, parent_flag, parent_id, data_offset, data_len);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ag_shredder_shred_batch(ag_rs_ctx* c, size_t nslices, size_t S, const uint8_t* parent_flags,
+                            const uint8_t* parent_ids, const uint8_t* data, size_t data_stride,
+                            const uint32_t* data_lens, const uint64_t* slots, const uint64_t* slice_indices,
+                            const uint8_t* is_last, const uint8_t* seed, const uint8_t* pk, uint8_t* codewords,
+                            uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets, size_t packet_stride,
+                            uint32_t* packet_lens) {
+  if (!c || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
+      (nslices && (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed ||
+                   !pk)))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  const size_t n = nslices, cw_stride = ag::kPipeShreds * S;
+  ShredderKind k;
+  shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
+  // 1. Slice::payload_bytes into the data regions, 2. ReedSolomonCoder::shred in place
+  std::vector<uint32_t> lens(n);
+  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
+                                lens.data());
+  if (st) return st;
+  if ((st = ag_rs_coder_shred_batch(c, k.m, n, S, nullptr, 0, lens.data(), codewords, cw_stride))) return st;
+  // 3. slice Merkle trees, 4. slice signatures, 5. the 64 datagrams per slice
+  return shred_tail(c, k, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
+                    sigs_out, packets, packet_stride, packet_lens, 0, nullptr, nullptr);
+}
+
+// RegularShredder::shred over slices of mixed shred sizes: the stages of ag_shredder_shred_batch,
+// each taking one size per slice -- the var coder (one launch set for the whole mix), the var
+// Merkle build over the size table the coder uploaded (d_lens: lens | sizes | column prefix; it
+// stays valid on the stream until the next coder call), the serializer with a row size per slice.
+int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* parent_flags, const uint8_t* parent_ids,
+                                const uint8_t* data, size_t data_stride, const uint32_t* data_lens,
+                                const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
+                                const uint8_t* seed, const uint8_t* pk, uint8_t* codewords, size_t codeword_stride,
+                                uint32_t* shred_bytes_out, uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets,
+                                size_t packet_stride, uint32_t* packet_lens, size_t nblocks,
+                                const uint32_t* block_counts, uint8_t* block_hashes_out) {
+  if (!c || nslices >= (size_t{1} << 24)) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return nblocks ? AG_RS_ERR_INVALID_ARGUMENT : AG_RS_OK;
+  if (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed || !pk ||
+      !codewords || !packets || !packet_lens || reinterpret_cast<uintptr_t>(codewords) % 16 || codeword_stride % 16)
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  const size_t n = nslices;
+  // every check on the host, before the first launch: the framing's, the strides', the blocks'
+  std::vector<uint32_t> lens(n);
+  size_t max_s = 0, max_len = 0;
+  for (size_t b = 0; b < n; ++b) {
+    if (parent_flags[b] > 1) return AG_RS_ERR_INVALID_ARGUMENT;
+    const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
+    if (framed > AG_SLICE_MAX_DATA) return AG_RS_ERR_TOO_MUCH_DATA;
+    size_t S = 0;
+    if (ag_rs_coder_shred_bytes(framed, &S)) return AG_RS_ERR_TOO_MUCH_DATA;
+    max_s = std::max(max_s, S);
+    max_len = std::max<size_t>(max_len, data_lens[b]);
+  }
+  size_t need = 0;
+  if (ag_shred_datagram_bytes(max_s, ag::kPipeHeight, &need) || packet_stride < need ||
+      codeword_stride < ag::kPipeShreds * max_s || (max_len && (!data || (n > 1 && data_stride < max_len))))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nblocks) {
+    if (!block_counts || !block_hashes_out || reinterpret_cast<uintptr_t>(block_hashes_out) % 16 || nblocks > n)
+      return AG_RS_ERR_INVALID_ARGUMENT;
+    size_t sum = 0;
+    for (size_t b = 0; b < nblocks; ++b) {
+      if (block_counts[b] == 0 || block_counts[b] > AG_BLOCK_MAX_SLICES) return AG_RS_ERR_INVALID_ARGUMENT;
+      sum += block_counts[b];
+    }
+    if (sum != n) return AG_RS_ERR_INVALID_ARGUMENT;
+  }
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  ShredderKind k;
+  shredder_kind(AG_SHREDDER_REGULAR, codeword_stride, &k);
+  k.group_stride = codeword_stride;  // rows packed at each slice's own size: addressed per slice
+  // 1. Slice::payload_bytes into the data regions (a framed payload is shorter than 32 * S_s, so
+  //    it stays inside its own slice's data shreds), 2. ReedSolomonCoder::shred in place
+  int st = ag_slice_frame_batch(c, n, max_s, parent_flags, parent_ids, data, data_stride, data_lens, codewords,
+                                codeword_stride, lens.data());
+  if (st) return st;
+  if ((st = ag_rs_coder_shred_batch_var(c, k.m, n, nullptr, 0, lens.data(), codewords, codeword_stride,
+                                        shred_bytes_out)))
+    return st;
+  if (!(c->last_encode_kernels & ag::kEkVar)) return AG_RS_ERR_DEVICE;  // (16-byte-aligned codewords: always var)
+  const uint32_t* d_sizes = c->d_lens.as<uint32_t>() + n;
+  // 3. slice Merkle trees, 4. slice signatures, 5. the 64 datagrams per slice (rows and data
+  //    lengths at the slice's own size), 6. the block hashes over the roots
+  return shred_tail(c, k, n, 0, d_sizes, codewords, codeword_stride, slots, slice_indices, is_last, seed, pk,
+                    roots_out, sigs_out, packets, packet_stride, packet_lens, nblocks, block_counts,
+                    block_hashes_out);
+}
+
+int ag_shredder_deshred_batch(ag_rs_ctx* c, size_t nslices, size_t S, uint8_t* packets, size_t packet_stride,
+                              uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords, int32_t* status,
+                              uint64_t* slots_out, uint64_t* slice_indices_out, uint8_t* is_last_out,
+                              uint8_t* parent_flags_out, uint8_t* parent_ids_out, uint32_t* data_offsets_out,
+                              uint32_t* data_lens_out) {
+  if (!c || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
+      (nslices && (!pk || !status || !slots_out || !slice_indices_out || !is_last_out || !parent_flags_out ||
+                   !parent_ids_out || !data_offsets_out || !data_lens_out)))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  const size_t n = nslices, N = n * ag::kPipeShreds, cw_stride = ag::kPipeShreds * S;
+  int st;
+  ShredderKind k;
+  shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
+  // 1-3. the kept shreds of every slice (payload rows straight into the codewords: row 64 s + j
+  //      is shard j of slice s), with every plausible shred's leaf digest kept for the Merkle
+  //      rebuild's level 0: step 5 hashes only the rows the coder restores or may rewrite
+  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
+  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream))) return st;
+  uint8_t* nodes = c->d_merkle_nodes.as<uint8_t>();
+  DeshredViews v;
+  if ((st = deshred_front(c, k, n, S, packets, packet_stride, packet_lens, pk, codewords, nodes, nodes_stride,
+                          ag::kPipeShreds, &v)))
+    return st;
+  const uint64_t* h_present = v.h.present;
+  // 4. ReedSolomonCoder::deshred over the kept shreds (restores the data shreds, re-encodes
+  //    all coding shreds, strips the padding); on the device for whole-chunk shreds
+  std::vector<int64_t> plen(n);
+  bool no_reencode = true;  // no surplus shreds and no slice with every data shred
+  for (size_t s = 0; s < n && no_reencode; ++s)
+    no_reencode = __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData) &&
+                  (h_present[s] & 0xFFFFFFFFull) != 0xFFFFFFFFull;
+  const bool device_coder = pipe_tail_ok(S, kDataShreds, no_reencode);
+  if (device_coder) {
+    if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, v.d_present, plen.data(), kDataShreds, no_reencode)))
+      return st;
+  } else {
+    std::vector<uint8_t> dp(n * ag::kPipeData), cp(n * k.m);
+    for (size_t s = 0; s < n; ++s) coder_flags(k, h_present[s], &dp[s * ag::kPipeData], &cp[s * k.m]);
+    if ((st = ag_rs_coder_deshred_batch(c, k.m, n, S, codewords, cw_stride, dp.data(), cp.data(), AG_RS_DECODE_ANY_K,
+                                        plen.data())))
+      return st;
+  }
+  // 5. check_merkle_tree: the rebuilt tree's root must be the signed one; its paths serve
+  //    the reconstructed datagrams.  Kept shreds the coder left as received reuse the digests
+  //    their proof check computed (same bytes); restored rows, and coding rows the re-encode
+  //    may have rewritten, are hashed again.
+  //    Invariant the reuse depends on: present ⊆ active ∧ proof-ok.  Every kept
+  //    shred (a bit of d_present, set by pipe_check only for shreds that were active in the
+  //    step-3 verify and whose derived root matched) had its leaf digest written to
+  //    d_merkle_nodes at (slice, index) by that verify; nothing between step 3 and here writes
+  //    those rows of the codeword or those nodes (the coder stage touches only absent rows
+  //    and, per the store masks, coding rows the leaf flags mark for re-hashing).  The verify
+  //    also stores digests of rows it then rejects: those rows are not in d_present, so the
+  //    flags below re-hash or ignore them.  A new step in between that writes kept rows or
+  //    d_merkle_nodes must clear the matching present bits or re-hash.
+  {
+    uint8_t *lflags, *llist;
+    if ((st = pipe_buf(c, kBufLeafFlags, N, &lflags)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &llist)) ||
+        (st = ensure_empty_roots(c)))
+      return st;
+    // the host coder path (shreds not whole 64-byte chunks) re-encodes every coding shred
+    if (ag::launch_pipe_leaf_flags(v.d_present, n, !device_coder, lflags, c->stream) != hipSuccess)
+      return AG_RS_ERR_DEVICE;
+    ag::MerkleBuildParams mb{};
+    mb.leaves = codewords;
+    mb.leaf_stride = S;
+    mb.slice_stride = cw_stride;
+    mb.leaf_bytes = static_cast<uint32_t>(S);
+    mb.n_leaves = ag::kPipeShreds;
+    mb.nslices = n;
+    mb.empty_roots = c->d_empty_roots.as<uint32_t>();
+    mb.roots = v.roots2;
+    mb.proofs = v.cols.proof;
+    mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
+    mb.hash_leaf = lflags;
+    mb.list = reinterpret_cast<uint32_t*>(llist);
+    c->last_merkle_kernels = 0;
+    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
+      return AG_RS_ERR_DEVICE;
+  }
+  uint8_t* same;
+  if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
+  if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  std::vector<uint8_t> h_same(n);
+  AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
+  // 6. SlicePayload::try_from
+  std::vector<uint8_t> sstat(n);
+  if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
+                                 parent_ids_out, data_offsets_out, data_lens_out)))
+    return st;  // synchronous: h_same has landed
+  // 6b. The crate's decoder reads every kept shred (reed_solomon.rs:154-166); the pass above
+  //     reads 32 of them (ANY_K).  On a consistent slice both restore the same bytes (MDS), and
+  //     a slice that passed check_merkle_tree is consistent: the rebuilt codeword matches the
+  //     signed root that commits every kept shred.  A slice that failed the padding or the
+  //     Merkle check with more than 32 kept shreds may hold an inconsistent shred the ANY_K
+  //     pass did not read (a leader signing a non-codeword), and the crate's bytes -- hence
+  //     the error, BadEncoding vs InvalidMerkleTree -- can differ.  Such slices are decoded
+  //     again from their received bytes with EXACT and re-checked, one by one (honest
+  //     leaders never produce them).
+  for (size_t s = 0; s < n; ++s) {
+    const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
+    if (!failed || __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData)) continue;
+    if ((st = pipe_rerun_exact(c, k, s, S, packets, packet_stride, packet_lens, v, codewords, same, &plen[s],
+                               &h_same[s], &sstat[s], parent_flags_out + s,
+                               parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s, data_offsets_out + s,
+                               data_lens_out + s)))
+      return st;
+  }
+  std::vector<uint8_t> ok(n);
+  pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
+                is_last_out);
+  // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
+  uint8_t* d_ok;
+  uint32_t* fresh;
+  if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  AG_HIP(hipStreamSynchronize(c->stream));  // host vectors read by async copies
+  return AG_RS_OK;
+}
+
+// ---- the other three shredders of shredder.rs composed (CodingOnly, PETS, AONT) -------------
+
+int ag_shredder_shred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_t S, const uint8_t* parent_flags,
+                                 const uint8_t* parent_ids, const uint8_t* data, size_t data_stride,
+                                 const uint32_t* data_lens, const uint64_t* slots, const uint64_t* slice_indices,
+                                 const uint8_t* is_last, const uint8_t* seed, const uint8_t* pk, const uint8_t* keys,
+                                 uint8_t* codewords, size_t cw_stride, uint8_t* roots_out, uint8_t* sigs_out,
+                                 uint8_t* packets, size_t packet_stride, uint32_t* packet_lens) {
+  if (kind == AG_SHREDDER_REGULAR) {
+    if (cw_stride != ag::kPipeShreds * S) return AG_RS_ERR_INVALID_ARGUMENT;
+    return ag_shredder_shred_batch(c, nslices, S, parent_flags, parent_ids, data, data_stride, data_lens, slots,
+                                   slice_indices, is_last, seed, pk, codewords, roots_out, sigs_out, packets,
+                                   packet_stride, packet_lens);
+  }
+  ShredderKind k;
+  if (!c || !shredder_kind(kind, cw_stride, &k) || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
+      cw_stride < (kDataShreds + k.m) * S || cw_stride % 4 ||
+      (nslices && (!parent_flags || !parent_ids || !data_lens || !slots || !slice_indices || !is_last || !seed ||
+                   !pk || (k.aon >= 0 && !keys))))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  const size_t n = nslices;
+  // MAX_DATA_SIZE: the key tail of PETS / AONT must fit the slice as well (shredder.rs:409, 457)
+  const size_t extra = k.aon >= 0 ? ag::kCipherKeyBytes : 0;
+  for (size_t b = 0; b < n; ++b) {
+    const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
+    if (framed + extra > kMaxPayload) return AG_RS_ERR_TOO_MUCH_DATA;
+  }
+  // 1. Slice::payload_bytes into the data regions; 2. PETS / AONT: encrypt_with_random_key with
+  //    the caller's key + the key tail; 3. ReedSolomonCoder::shred in place
+  std::vector<uint32_t> lens(n);
+  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
+                                lens.data());
+  if (st) return st;
+  if (k.aon >= 0) {
+    if ((st = ag_aon_encrypt_batch(c, k.aon, n, keys, codewords, cw_stride, lens.data()))) return st;
+    for (uint32_t& l : lens) l += static_cast<uint32_t>(ag::kCipherKeyBytes);
+  }
+  if ((st = ag_rs_coder_shred_batch(c, k.m, n, S, nullptr, 0, lens.data(), codewords, cw_stride))) return st;
+  // 4. the 64 output shreds (data first) in place: Merkle tree, signature, datagrams over them
+  return shred_tail(c, k, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
+                    sigs_out, packets, packet_stride, packet_lens, 0, nullptr, nullptr);
+}
+
+int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_t S, uint8_t* packets,
+                                   size_t packet_stride, uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords,
+                                   size_t cw_stride, int32_t* status, uint64_t* slots_out, uint64_t* slice_indices_out,
+                                   uint8_t* is_last_out, uint8_t* parent_flags_out, uint8_t* parent_ids_out,
+                                   uint32_t* data_offsets_out, uint32_t* data_lens_out) {
+  if (kind == AG_SHREDDER_REGULAR) {
+    if (cw_stride != ag::kPipeShreds * S) return AG_RS_ERR_INVALID_ARGUMENT;
+    return ag_shredder_deshred_batch(c, nslices, S, packets, packet_stride, packet_lens, pk, codewords, status,
+                                     slots_out, slice_indices_out, is_last_out, parent_flags_out, parent_ids_out,
+                                     data_offsets_out, data_lens_out);
+  }
+  ShredderKind k;
+  if (!c || !shredder_kind(kind, cw_stride, &k) || !pipe_args_ok(nslices, S, codewords, packets, packet_lens) ||
+      cw_stride < (kDataShreds + k.m) * S || cw_stride % 4 ||
+      (nslices && (!pk || !status || !slots_out || !slice_indices_out || !is_last_out || !parent_flags_out ||
+                   !parent_ids_out || !data_offsets_out || !data_lens_out)))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  const size_t n = nslices;
+  int st;
+  // Pass 0 decodes with ANY_K on the device (per-slice window patterns, no host per-slice work);
+  // a slice with surplus kept shreds that then fails some check could decode differently under
+  // the crate's decoder over every kept shred, so the batch is redone with EXACT (pass 1).  A
+  // slice that passes every check decoded the codeword its signed root commits, which every
+  // kept shred matches: EXACT agrees there.  The packets' lengths change only
+  // in step 7 (PETS / AONT serialize the absent datagrams before decrypting, into length-0 slots
+  // that a redo parses as absent), so the redo starts from the same datagrams.
+  DeshredViews v;
+  std::vector<uint8_t> ok(n), pre_ok(n);
+  uint8_t* d_ok = nullptr;
+  uint32_t* fresh = nullptr;
+  const bool fast_ok = pipe_tail_ok(S, k.m, true) && n > 1 && k.m >= kDataShreds && k.m <= 2 * kDataShreds;
+  auto run_pass = [&](int pass, bool* redo) -> int {
+    // 1-3. the kept shreds of every slice (the Regular pipeline's steps with this shredder's data
+    //      / coding layout), payloads parsed straight into their codeword rows
+    if ((st = deshred_front(c, k, n, S, packets, packet_stride, packet_lens, pk, codewords, nullptr, 0, 0, &v)))
+      return st;
+    const uint64_t* h_present = v.h.present;
+    // 4. deshred_validated_shreds: ReedSolomonCoder::deshred over the kept shreds (in their
+    //    codeword rows already), then decrypt_payload (PETS / AONT) after the raw shreds are
+    //    taken.  Pass 0: ANY_K with the window patterns built on the device from the kept
+    //    shreds' codeword-row words; pass 1: the crate's decoder over every kept shred (EXACT)
+    std::vector<int64_t> plen(n);
+    bool surplus = false;
+    for (size_t s = 0; s < n; ++s) surplus |= __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
+    bool full_data = false;
+    if (kind == AG_SHREDDER_AONT)
+      for (size_t s = 0; s < n; ++s) full_data |= (h_present[s] & 0xFFFFFFFFull) == 0xFFFFFFFFull;
+    if (pass == 0 && pipe_tail_ok(S, k.m, !surplus && !full_data)) {
+      // codeword-row present words (pipe_coder_deshred: data | coding 0..31 << 32, coding
+      // 32..63 in word 1 when m > 32); AONT's rows are the codeword rows
+      const size_t wps = k.m > kDataShreds ? 2 : 1;
+      const uint64_t* words = v.d_present;
+      if (kind != AG_SHREDDER_AONT) {
+        uint8_t* dw;
+        if ((st = pipe_buf(c, kBufCoderWords, 8 * wps * n, &dw)) || (st = c->h_strip.ensure(8 * wps * n))) return st;
+        uint64_t* hw = c->h_strip.as<uint64_t>();
+        for (size_t s = 0; s < n; ++s) {
+          const uint64_t o = h_present[s];
+          if (kind == AG_SHREDDER_CODING_ONLY) {  // output j = coding j
+            hw[2 * s] = (o & 0xFFFFFFFFull) << 32;
+            hw[2 * s + 1] = o >> 32;
+          } else {  // PETS: output j < 31 = data j, output 31 + i = coding i
+            hw[2 * s] = (o & 0x7FFFFFFFull) | (((o >> 31) & 0xFFFFFFFFull) << 32);
+            hw[2 * s + 1] = o >> 63;
+          }
+        }
+        AG_HIP(hipMemcpyAsync(dw, hw, 8 * wps * n, hipMemcpyHostToDevice, c->stream));
+        words = reinterpret_cast<const uint64_t*>(dw);
+      }
+      // (pipe_coder_deshred reads its results back through h_strip after the upload completed)
+      if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, words, plen.data(), k.m, !surplus && !full_data)))
+        return st;
+    } else {
+      std::vector<uint8_t> dp(n * kDataShreds, 0), cp(n * k.m, 0);
+      for (size_t s = 0; s < n; ++s) coder_flags(k, h_present[s], &dp[s * kDataShreds], &cp[s * k.m]);
+      if ((st = ag_rs_coder_deshred_batch(c, k.m, n, S, codewords, cw_stride, dp.data(), cp.data(), AG_RS_DECODE_EXACT,
+                                          plen.data())))
+        return st;
+    }
+    // AONT: the SHA-256 of every decoded ciphertext (decrypt_payload's key mask) runs on the side
+    // stream, overlapping the Merkle rebuild, the root comparison and the absent datagrams'
+    // serialization below (all of them only read the rows); one SHA-256 chain per slice leaves
+    // most of the chip's issue slots to them
+    bool sha_side = false;
+    if (k.aon == AG_AON_AONT) {
+      std::vector<uint32_t> shl(n);
+      uint32_t mx = ag::kCipherKeyBytes;
+      for (size_t s = 0; s < n; ++s) {
+        shl[s] = plen[s] >= static_cast<int64_t>(ag::kCipherKeyBytes) ? static_cast<uint32_t>(plen[s])
+                                                                      : static_cast<uint32_t>(ag::kCipherKeyBytes);
+        mx = std::max(mx, shl[s]);
+      }
+      if ((st = c->d_aon_lens2.ensure(n * 4, c->stream)) || (st = c->d_aon_digests.ensure(n * 32, c->stream)))
+        return st;
+      AG_HIP(hipStreamSynchronize(c->stream));
+      AG_HIP(hipMemcpy(c->d_aon_lens2.ptr, shl.data(), n * 4, hipMemcpyHostToDevice));
+      ag::BufferBatch sb;
+      sb.base = codewords;
+      sb.stride = cw_stride;
+      sb.lens = c->d_aon_lens2.as<uint32_t>();
+      sb.n = n;
+      sb.max_len = mx;
+      AG_HIP(hipEventRecord(c->side_fork, c->stream));
+      AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
+      if (ag::launch_sha256(sb, ag::kCipherKeyBytes, c->d_aon_digests.as<uint8_t>(), c->side) != hipSuccess)
+        return AG_RS_ERR_DEVICE;
+      AG_HIP(hipEventRecord(c->side_join, c->side));
+      sha_side = true;
+    }
+    // 5. check_merkle_tree over the raw output shreds (before any decryption: they are the
+    //    codeword rows)
+    if ((st = kind_merkle(c, k, n, S, codewords, cw_stride, v.roots2, v.cols.proof))) return st;
+    uint8_t* same;
+    if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
+    if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+    std::vector<uint8_t> h_same(n);
+    AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
+    AG_HIP(hipStreamSynchronize(c->stream));
+    if (k.aon >= 0) {
+      // the absent datagrams of the slices that decoded and match their root, serialized from
+      // the encrypted rows; then decrypt_payload (BadEncoding for a failed key check)
+      for (size_t s = 0; s < n; ++s) pre_ok[s] = plen[s] >= 0 && h_same[s];
+      if ((st = fill_missing(c, k, n, S, v, pre_ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+      AG_HIP(hipStreamSynchronize(c->stream));
+      std::vector<uint32_t> cl(n);
+      for (size_t s = 0; s < n; ++s) cl[s] = pre_ok[s] ? static_cast<uint32_t>(plen[s]) : 0;
+      std::vector<int64_t> pl(n);
+      if (sha_side) {
+        // decrypt_payload with the side stream's digests (ag_aon_decrypt_batch's key and
+        // length rules; the digests of the slices decrypted here hash the same lengths)
+        for (size_t s = 0; s < n; ++s) {
+          pl[s] = cl[s] < ag::kCipherKeyBytes ? -AG_RS_ERR_BAD_ENCODING
+                                              : static_cast<int64_t>(cl[s]) - ag::kCipherKeyBytes;
+          if (cl[s] < ag::kCipherKeyBytes) cl[s] = ag::kCipherKeyBytes;  // no-op
+        }
+        ag::BufferBatch bb;
+        if ((st = aon_batch(c, n, codewords, cw_stride, cl.data(), 0, &bb)) ||
+            (st = c->d_aon_keys.ensure(n * 16, c->stream)))
+          return st;
+        AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
+        if (ag::launch_derive_keys(bb, 1, c->d_aon_digests.as<uint8_t>(), c->d_aon_keys.as<uint8_t>(), c->stream) !=
+                hipSuccess ||
+            ag::launch_apply_keystream(bb, c->d_aon_keys.as<uint8_t>(), ag::kCipherKeyBytes, c->stream) != hipSuccess)
+          return AG_RS_ERR_DEVICE;
+        AG_HIP(hipStreamSynchronize(c->stream));
+      } else if ((st = ag_aon_decrypt_batch(c, k.aon, n, codewords, cw_stride, cl.data(), pl.data()))) {
+        return st;
+      }
+      for (size_t s = 0; s < n; ++s)
+        if (pre_ok[s]) plen[s] = pl[s];
+    }
+    // 6. SlicePayload::try_from on the (decrypted) payload
+    std::vector<uint8_t> sstat(n);
+    if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
+                                   parent_ids_out, data_offsets_out, data_lens_out)))
+      return st;
+    pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
+                  is_last_out);
+    for (size_t s = 0; s < n; ++s)
+      *redo |= !ok[s] && __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
+    return AG_RS_OK;
+  };
+  for (int pass = fast_ok ? 0 : 1; pass < 2; ++pass) {
+    bool redo = false;
+    // the side-stream rule for AONT's SHA-256, which a pass forks in step 4 and joins in step
+    // 5's decrypt: an error anywhere in a pass drains the side stream
+    if ((st = run_pass(pass, &redo))) return drain_side(c, st);
+    if (!redo) break;
+  }
+  // 7. fill_missing_shreds: every absent slot of a successful slice gets its datagram (PETS /
+  //    AONT serialized theirs from the encrypted rows, before the decrypt)
+  if (k.aon < 0) {
+    if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+    AG_HIP(hipStreamSynchronize(c->stream));
+  }
+  AG_HIP(hipMemcpyAsync(d_ok, ok.data(), n, hipMemcpyHostToDevice, c->stream));
+  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  AG_HIP(hipStreamSynchronize(c->stream));
+  return AG_RS_OK;
+}
+
+}  // extern "C"

@@ -111,14 +111,15 @@ def _deshred(ctx, dev, rows, pk, S):
     return res, _packets(d_buf, d_ln, n), cw.cpu().numpy()
 
 
-def _expect(rows, pk_bytes, S):
-    """The oracle's verdict for every slice: receive (the receiver's checks) + Shredder::deshred
-    with the crate's decoder over every kept shred, and the datagram slots after the call
-    (kept ones as received, the others filled for a successful slice, untouched otherwise)."""
+def _expect(rows, pk_bytes, S, kind=so.REGULAR):
+    """The oracle's verdict for every slice: receive (the receiver's checks, with the shredder's
+    data / coding layout) + Shredder::deshred with the crate's decoder over every kept shred,
+    and the datagram slots after the call (kept ones as received, the others filled for a
+    successful slice, untouched otherwise)."""
     out = []
     for r in rows:
-        kept = so.receive(r, pk_bytes, S)
-        st, res = so.deshred(kept)
+        kept = so.receive(r, pk_bytes, S, so.DATA_OUT[kind])
+        st, res = so.deshred_kind(kept, kind)
         if st == so.OK:
             slots = [r[j] if kept[j] is not None else res["datagrams"][j] for j in range(64)]
         else:
@@ -127,7 +128,9 @@ def _expect(rows, pk_bytes, S):
     return out
 
 
-def _check_against_oracle(res, out, cw, want):
+def _check_against_oracle(res, out, cw, want, raw_shreds=True):
+    """Verdicts, datagram slots, headers and payload bytes against _expect's; raw_shreds: the
+    codeword rows are the slice's raw shreds too (Regular: its codeword is the 64 output shreds)."""
     assert res.status.tolist() == [w[0] for w in want], \
         ([rs.STATUS_KIND.get(int(x), int(x)) for x in res.status], [w[0] for w in want])
     for b, (st, r, slots) in enumerate(want):
@@ -138,7 +141,8 @@ def _check_against_oracle(res, out, cw, want):
         assert res.parents[b] == r["parent"]
         off, n = int(res.data_offsets[b]), int(res.data_lens[b])
         assert cw[b, off:off + n].tobytes() == r["data"]
-        assert cw[b].tobytes() == b"".join(r["raw"].data + r["raw"].coding)
+        if raw_shreds:
+            assert cw[b].tobytes() == b"".join(r["raw"].data + r["raw"].coding)
 
 
 def _non_codeword(slice_, tamper):
@@ -372,26 +376,45 @@ def test_deshred_batch_kind_matches_oracle(ctx, dev, kind, S):
             bad[40] ^= 1  # no longer derives the signed root: dropped by the receiver
             row[t] = bytes(bad)
         inp.append(row)
-    want = []
-    for r in inp:
-        kept = so.receive(r, pk_bytes, S, nd)
-        st, res = so.deshred_kind(kept, kind)
-        slots = ([r[j] if kept[j] is not None else res["datagrams"][j] for j in range(64)] if st == so.OK
-                 else [x if x is not None else b"" for x in r])
-        want.append((st, res, slots))
+    want = _expect(inp, pk_bytes, S, kind)
     assert want[4][0] == so.NOT_ENOUGH_SHARDS and sum(w[0] == so.OK for w in want) >= 6
     pk = _dev(np.frombuffer(pk_bytes, np.uint8), dev)
     res, out, cw = _deshred_kind(ctx, dev, kind, inp, pk, S)
-    assert res.status.tolist() == [w[0] for w in want]
-    stride = _stride(kind, S)
-    for b, (st, r, slots) in enumerate(want):
-        assert out[b] == slots, b
-        if st != so.OK:
-            continue
-        assert (int(res.slots[b]), int(res.slice_indices[b]), bool(res.is_last[b])) == r["header"]
-        assert res.parents[b] == r["parent"]
-        off, ln = int(res.data_offsets[b]), int(res.data_lens[b])
-        assert cw[b, off:off + ln].tobytes() == r["data"]
+    _check_against_oracle(res, out, cw, want, raw_shreds=False)
+
+
+def test_deshred_batches_share_one_context(ctx, dev):
+    """The composed shredders' scratch is one table per context, shared by every entry point and
+    grown on demand: deshreds of different shredders and batch sizes back to back on one context
+    (Regular 6 slices, PETS 3, AONT 6, Regular 2, CodingOnly 3; S = 64) must each still equal the
+    oracle.  Every slice arrives as a random 32..64 of its datagrams; the second slice of every
+    batch comes from a leader that altered one shred after encoding and arrives with surplus
+    shreds, so Regular decodes it again with EXACT and the others redo their batch (pass 1)."""
+    S = 64
+    pk_bytes = ed.secret_to_public(SEED)
+    pk = _dev(np.frombuffer(pk_bytes, np.uint8), dev)
+    batches = [(so.REGULAR, 6), (so.PETS, 3), (so.AONT, 6), (so.REGULAR, 2), (so.CODING_ONLY, 3)]
+    for i, (kind, n) in enumerate(batches):
+        rng = random.Random(4100 + i)
+        nd = so.DATA_OUT[kind]
+        inp = []
+        for b, (parent, data, slot, si, last, key) in enumerate(_slices_kind(rng, n, S, kind)):
+            rows, raw, _, _ = so.shred_kind(kind, parent, data, slot, si, last, SEED, key)
+            if b == 1:  # a leader that signs a non-codeword
+                shards = list(raw.data) + list(raw.coding)
+                t = rng.randrange(64)
+                shards[t] = bytes(x ^ 0x5A for x in shards[t])
+                rows = so.datagrams(shards[:nd], shards[nd:], slot, si, last, SEED)[0]
+            keep = set(rng.sample(range(64), rng.randrange(33 if b == 1 else 32, 65)))
+            inp.append([rows[j] if j in keep else None for j in range(64)])
+        want = _expect(inp, pk_bytes, S, kind)
+        # no decode of a signed non-codeword rebuilds its tree: the slice fails, with surplus shreds
+        assert want[1][0] in (so.BAD_ENCODING, so.INVALID_MERKLE_TREE), (i, want[1][0])
+        if kind == so.REGULAR:
+            res, out, cw = _deshred(ctx, dev, inp, pk, S)
+        else:
+            res, out, cw = _deshred_kind(ctx, dev, kind, inp, pk, S)
+        _check_against_oracle(res, out, cw, want, raw_shreds=kind == so.REGULAR)
 
 
 @pytest.mark.parametrize("kind", KINDS)
