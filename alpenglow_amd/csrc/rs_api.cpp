@@ -16,7 +16,6 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <immintrin.h>
 #include <memory>
 #include <new>
 #include <vector>
@@ -33,997 +32,19 @@
 #include "rs_patterns.hpp"
 #include "shredder.hpp"
 
-using namespace ag::host;  // the context's buffers and the helpers shared with shredder_api.cpp
-using ag::build_corr_pattern;
-using ag::build_syn_pattern;
-using ag::corr_fits;
+using namespace ag::host;  // the context's buffers and the helpers shared with the other host files
 using ag::count_flags;
-using ag::gf_invert;
-using ag::next_pow2;
+using ag::lowrate_chunk;
+using ag::mc_chunk;
 using ag::pack_flags;
-using ag::window128_masks;
-using ag::window64_masks;
+using ag::pack_present_words;
+using ag::padded_shard;
+using ag::xform_points;
 
 namespace {
 
-int check_geometry(size_t k, size_t m, size_t S) {
-  if (ag::use_high_rate(k, m) < 0) return AG_RS_ERR_UNSUPPORTED_SHARD_COUNT;
-  if (S == 0 || S % 2) return AG_RS_ERR_INVALID_SHARD_SIZE;
-  if (S > 0xFFFFFFFEull) return AG_RS_ERR_INVALID_ARGUMENT;
-  return AG_RS_OK;
-}
-
-
-// Single-chunk HighRate geometries served by the bitsliced N-point transform kernel:
-// k <= N, next_pow2(m) == N, N in {32, 64}, whole 64-byte chunks.  Returns N or 0.
-// (HighRate with a single chunk implies next_pow2(k) == N and k <= m.)
-unsigned xform_points(size_t k, size_t m, size_t S) {
-  if (S == 0 || S % 64 || ag::use_high_rate(k, m) != 1) return 0;
-  const size_t n = next_pow2(m);
-  return (n == 32 || n == 64) && k <= n ? static_cast<unsigned>(n) : 0;
-}
-
-// Multi-chunk HighRate encode with a small recovery chunk (encode_mc kernel): returns the
-// chunk next_pow2(m) in {1, 2, 4} when k > chunk, k <= 64, whole 64-byte chunks; else 0.
-unsigned mc_chunk(size_t k, size_t m, size_t S) {
-  if (S == 0 || S % 64 || ag::use_high_rate(k, m) != 1 || k > 64) return 0;
-  const size_t c = next_pow2(m);
-  return c <= 4 && k > c ? static_cast<unsigned>(c) : 0;
-}
-
-// LowRate encode through the transform kernel, one launch per recovery chunk: returns the
-// chunk next_pow2(k) in {32, 64} when the recovery chunks fit the launcher, else 0.
-unsigned lowrate_chunk(size_t k, size_t m, size_t S) {
-  if (S == 0 || S % 64 || ag::use_high_rate(k, m) != 0) return 0;
-  const size_t c = next_pow2(k);
-  const size_t chunks = (m + c - 1) / c;
-  if (c == 32 && chunks <= 4) return 32;
-  if (c == 64 && chunks <= 3) return 64;
-  return 0;
-}
-
 // Host-memory calls: bytes (in + out) per staging group; two groups in flight.
 constexpr size_t kStageGroupBytes = size_t{64} << 20;
-
-// Scratch budget of the generic kernels (per launch).
-constexpr size_t kGenericScratchBytes = size_t{512} << 20;
-
-// Restrided shard buffer (shard sizes that are not whole 64-byte chunks), per group.
-constexpr size_t kRestrideGroupBytes = size_t{2048} << 20;
-
-int encode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, const uint8_t* orig,
-                  size_t ostride, uint8_t* rec, size_t rstride);
-
-// Shard sizes that are not whole 64-byte chunks (a slice's tail, reed_solomon.rs:94-95):
-// the whole chunks of every shard run in place on the bitsliced kernels (shard stride S,
-// chunks_per_shard = S / 64: the kernels take any alignment), and only the T = S mod 64 tail
-// bytes of each shard -- in the crate's tail layout exactly a T-byte shard --
-// are restrided into a padded 64-byte chunk per shard (restride_kernel), run there and
-// restrided back.  Taken when the padded geometry has a bitsliced path.
-size_t padded_shard(size_t S) { return (S + 63) / 64 * 64; }
-// Byte-odd buffers or strides: every shard goes through the restride (its byte path)
-bool odd_layout(const void* a, const void* b, size_t sa, size_t sb) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | sa | sb) & 1) != 0;
-}
-
-// Virtual shards of Sv bytes at byte `off` of every shard (shard stride sstride) are packed
-// into padded shards, encoded there, and the recovery shards' pieces unpacked.
-int encode_restrided(ag_rs_ctx* c, size_t k, size_t m, size_t Sv, size_t sstride, size_t off, size_t nblocks,
-                     const uint8_t* orig, size_t ostride, uint8_t* rec, size_t rstride) {
-  const size_t Sp = padded_shard(Sv), per_block = (k + m) * Sp;
-  const size_t group = std::max<size_t>(1, kRestrideGroupBytes / per_block);
-  int st = c->stage_pad.ensure(std::min(group, nblocks) * per_block, c->stream);
-  if (st) return st;
-  c->last_encode_kernels |= ag::kEkRestride;
-  uint8_t* pad = c->stage_pad.as<uint8_t>();
-  for (size_t b0 = 0; b0 < nblocks; b0 += group) {
-    const size_t nb = std::min(group, nblocks - b0);
-    if (ag::launch_restride(orig + b0 * ostride + off, ostride, sstride, pad, per_block, Sp, static_cast<uint32_t>(Sv),
-                            static_cast<uint32_t>(k), nb, false, nullptr, false, c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-    if ((st = encode_device(c, k, m, Sp, nb, pad, per_block, pad + k * Sp, per_block))) return st;
-    if (ag::launch_restride(pad + k * Sp, per_block, Sp, rec + b0 * rstride + off, rstride, sstride,
-                            static_cast<uint32_t>(Sv), static_cast<uint32_t>(m), nb, true, nullptr, false,
-                            c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-  }
-  return AG_RS_OK;
-}
-
-// The encode over the first S bytes of every shard (S % 64 == 0 on the bitsliced paths;
-// shards sstride >= S bytes apart).
-int encode_cols(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t sstride, size_t nblocks, const uint8_t* orig,
-                size_t ostride, uint8_t* rec, size_t rstride) {
-  const unsigned npts = xform_points(k, m, S);
-  const unsigned mc = mc_chunk(k, m, S);
-  const unsigned lr = lowrate_chunk(k, m, S);
-  if (npts || mc || lr) {
-    ag::XformParams p{};
-    p.in = orig;
-    p.in_block_stride = ostride;
-    p.in_shard_stride = sstride;
-    p.out = rec;
-    p.out_block_stride = rstride;
-    p.out_shard_stride = sstride;
-    p.n_in = static_cast<uint32_t>(k);
-    p.n_out = static_cast<uint32_t>(m);
-    p.chunks_per_shard = static_cast<uint32_t>(S / 64);
-    p.total_columns = static_cast<uint64_t>(nblocks) * (S / 64);
-    hipError_t e = hipSuccess;
-    if (npts) {
-      c->last_encode_kernels |= npts == 32 ? ag::encode32_kernel(p) : ag::kEkXformH8;
-      e = ag::launch_xform(npts == 32 ? ag::XformKind::kEncode32 : ag::XformKind::kEncode64, p, c->stream);
-    } else if (mc) {
-      c->last_encode_kernels |= ag::kEkEncodeMc;
-      e = ag::launch_encode_mc(mc, p, c->stream);
-    } else {
-      for (size_t j = 0; j * lr < m && e == hipSuccess;) {  // one launch per recovery chunk
-        ag::XformParams pj = p;
-        pj.out = rec + j * lr * sstride;
-        if (lr == 32 && j % 2 == 0 && (j + 1) * lr < m && j < 4) {  // chunks j, j + 1 in one launch
-          pj.n_out = static_cast<uint32_t>(std::min<size_t>(2 * lr, m - j * lr));
-          c->last_encode_kernels |= ag::kEkLowRate2;
-          e = ag::launch_xform_lowrate2(static_cast<unsigned>(j / 2), pj, c->stream);
-          j += 2;
-          continue;
-        }
-        pj.n_out = static_cast<uint32_t>(std::min<size_t>(lr, m - j * lr));
-        c->last_encode_kernels |= ag::kEkLowRate;
-        e = ag::launch_xform_lowrate(lr, static_cast<unsigned>(j), pj, c->stream);
-        ++j;
-      }
-    }
-    return e == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
-  }
-  int st = c->ensure_tables();
-  if (st) return st;
-  const int hr = ag::use_high_rate(k, m);
-  const size_t chunk = hr ? next_pow2(m) : next_pow2(k);
-  const size_t cover = hr ? k : m;
-  const size_t rows = std::max(chunk, (cover + chunk - 1) / chunk * chunk);
-  const size_t nsym = S / 2;
-  const size_t per_block = rows * nsym * 2;
-  const size_t per_launch = std::max<size_t>(1, kGenericScratchBytes / per_block);
-  if ((st = c->scratch.ensure(std::min(per_launch, nblocks) * per_block, c->stream))) return st;
-  for (size_t b0 = 0; b0 < nblocks; b0 += per_launch) {
-    ag::GenericEncodeParams p{};
-    p.orig = orig + b0 * ostride;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.rec = rec + b0 * rstride;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.k = static_cast<uint32_t>(k);
-    p.m = static_cast<uint32_t>(m);
-    p.high_rate = static_cast<uint32_t>(hr);
-    p.chunk = static_cast<uint32_t>(chunk);
-    p.rows = static_cast<uint32_t>(rows);
-    p.shard_bytes = static_cast<uint32_t>(S);
-    p.nsym = static_cast<uint32_t>(nsym);
-    p.nblocks = std::min(per_launch, nblocks - b0);
-    p.scratch = c->scratch.as<uint16_t>();
-    p.t = c->dtables();
-    c->last_encode_kernels |= ag::kEkGeneric;
-    if (ag::launch_generic_encode(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  return AG_RS_OK;
-}
-
-// A 32-point transform over shards that end in a split tail chunk, one launch on the caller's
-// buffers (no restride): chunks_per_shard = ceil(S / 64), the last chunk of every shard read
-// and written as 16-byte windows of its tail (rs_xform.hpp tile_io_g).  (Two launches -- the
-// whole chunks with the tails skipped, then the tails alone -- measured slower: 3.76 / 4.06
-// TB/s at S = 1000 against 3.8-4.0 / 4.2-4.4; the whole-chunk pass alone ran at 4.35 TB/s,
-// its shards' last 64-byte sectors left partial for the second pass to complete,
-// profiles/r05_tail_split_kernel_stats.csv.)
-int launch_tail(ag_rs_ctx* c, ag::XformKind kind, const ag::XformParams& p, bool encode) {
-  if (encode) c->last_encode_kernels |= ag::encode32_kernel(p);
-  return ag::launch_xform(kind, p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
-}
-
-// 32-point encodes of shards ending in a split tail chunk (S % 64 != 0, S even): the TAIL
-// transforms read and write the tail in place (launch_tail), no restride
-int encode_tail32(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, const uint8_t* orig, size_t ostride,
-                  uint8_t* rec, size_t rstride) {
-  const size_t cps = padded_shard(S) / 64;
-  ag::XformParams p{};
-  p.in = orig;
-  p.in_block_stride = ostride;
-  p.in_shard_stride = S;
-  p.out = rec;
-  p.out_block_stride = rstride;
-  p.out_shard_stride = S;
-  p.n_in = static_cast<uint32_t>(k);
-  p.n_out = static_cast<uint32_t>(m);
-  p.chunks_per_shard = static_cast<uint32_t>(cps);
-  p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-  p.tail_bytes = static_cast<uint32_t>(S % 64);
-  return launch_tail(c, ag::XformKind::kEncode32, p, true);
-}
-
-int encode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, const uint8_t* orig,
-                  size_t ostride, uint8_t* rec, size_t rstride) {
-  if (nblocks == 0) return AG_RS_OK;
-  const size_t Sp = padded_shard(S);
-  if (S % 2 == 0 && (xform_points(k, m, Sp) || mc_chunk(k, m, Sp) || lowrate_chunk(k, m, Sp))) {
-    if (odd_layout(orig, rec, ostride, rstride))
-      return encode_restrided(c, k, m, S, S, 0, nblocks, orig, ostride, rec, rstride);
-    const size_t full = S / 64 * 64, tail = S - full;
-    if (tail >= 16 && xform_points(k, m, Sp) == 32)  // (tail windows are 16 bytes of the tail itself)
-      return encode_tail32(c, k, m, S, nblocks, orig, ostride, rec, rstride);
-    int st;
-    if (full && (st = encode_cols(c, k, m, full, S, nblocks, orig, ostride, rec, rstride))) return st;
-    if (tail && (st = encode_restrided(c, k, m, tail, S, full, nblocks, orig, ostride, rec, rstride))) return st;
-    return AG_RS_OK;
-  }
-  return encode_cols(c, k, m, S, S, nblocks, orig, ostride, rec, rstride);
-}
-
-int decode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
-                  const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres, size_t npat,
-                  int mode);
-
-// ag_rs_coder_deshred_batch's flag packer (below): word b = data flags | coding 0..31 << 32
-bool pack_present_words(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n, uint64_t* pres,
-                        bool* any_full_data);
-
-// The decode counterpart of encode_restrided: originals and recovery shards of a group of
-// blocks go to one padded buffer, the bitsliced decoders run there, and only the restored
-// originals are restrided back (a store mask per pattern).
-int decode_restrided(ag_rs_ctx* c, size_t k, size_t m, size_t Sv, size_t sstride, size_t off, size_t nblocks,
-                     uint8_t* orig, size_t ostride, const uint8_t* rec, size_t rstride, const uint8_t* opres,
-                     const uint8_t* rpres, size_t npat, int mode) {
-  const size_t Sp = padded_shard(Sv), per_block = (k + m) * Sp;
-  // store masks: the absent originals of each pattern (k <= 64 on every bitsliced path)
-  // and the pack masks: only present shards are packed (decoders never read absent ones)
-  std::vector<uint64_t> mask(3 * npat);
-  const uint64_t kmask = k >= 64 ? ~uint64_t{0} : (uint64_t{1} << k) - 1;
-  const bool rmask = m <= 64;
-  if (k == 32 && m == 32) {  // the flags packed 32 at a time (AVX2 where the host has it)
-    std::vector<uint64_t> w(npat);
-    bool full_data = false;
-    (void)pack_present_words(opres, rpres, m, npat, w.data(), &full_data);
-    for (size_t p = 0; p < npat; ++p) {
-      if (__builtin_popcountll(w[p]) < 32) return AG_RS_ERR_NOT_ENOUGH_SHARDS;  // nothing launched yet
-      mask[p] = ~w[p] & kmask;
-      mask[npat + p] = w[p] & kmask;
-      mask[2 * npat + p] = w[p] >> 32;
-    }
-  } else {
-    for (size_t p = 0; p < npat; ++p)  // NotEnoughShards before anything is launched
-      if (count_flags(opres + p * k, k) + count_flags(rpres + p * m, m) < k) return AG_RS_ERR_NOT_ENOUGH_SHARDS;
-    for (size_t p = 0; p < npat; ++p) {
-      mask[p] = ~pack_flags(opres + p * k, k) & kmask;
-      mask[npat + p] = pack_flags(opres + p * k, k);
-      mask[2 * npat + p] = rmask ? pack_flags(rpres + p * m, m) : 0;
-    }
-  }
-  // upload only when the masks changed (steady-state batches reuse them, no sync)
-  int st;
-  if (mask != c->stage_mask_host) {
-    AG_HIP(hipStreamSynchronize(c->stream));  // queued restrides / a pending upload may read the old masks
-    if ((st = c->stage_mask.ensure(3 * npat * 8, c->stream))) return st;
-    c->stage_mask_host = std::move(mask);
-    if (hipMemcpyAsync(c->stage_mask.ptr, c->stage_mask_host.data(), 3 * npat * 8, hipMemcpyHostToDevice,
-                       c->stream) != hipSuccess) {
-      c->stage_mask_host.clear();  // never matches a mask set (3 * npat >= 3 words)
-      return AG_RS_ERR_DEVICE;
-    }
-  }
-  const uint64_t* d_omask = c->stage_mask.as<uint64_t>() + npat;
-  const uint64_t* d_rmask = rmask ? c->stage_mask.as<uint64_t>() + 2 * npat : nullptr;
-  const size_t group = std::max<size_t>(1, kRestrideGroupBytes / per_block);
-  if ((st = c->stage_pad.ensure(std::min(group, nblocks) * per_block, c->stream))) return st;
-  uint8_t* pad = c->stage_pad.as<uint8_t>();
-  for (size_t b0 = 0; b0 < nblocks; b0 += group) {
-    const size_t nb = std::min(group, nblocks - b0);
-    const size_t p0 = npat > 1 ? b0 : 0, np = npat > 1 ? nb : 1;
-    if (ag::launch_restride(orig + b0 * ostride + off, ostride, sstride, pad, per_block, Sp, static_cast<uint32_t>(Sv),
-                            static_cast<uint32_t>(k), nb, false, d_omask + p0, npat > 1, c->stream) != hipSuccess ||
-        ag::launch_restride(rec + b0 * rstride + off, rstride, sstride, pad + k * Sp, per_block, Sp,
-                            static_cast<uint32_t>(Sv), static_cast<uint32_t>(m), nb, false,
-                            d_rmask ? d_rmask + p0 : nullptr, npat > 1, c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-    if ((st = decode_device(c, k, m, Sp, nb, pad, per_block, pad + k * Sp, per_block, opres + p0 * k, rpres + p0 * m,
-                            np, mode)))
-      return st;
-    if (ag::launch_restride(pad, per_block, Sp, orig + b0 * ostride + off, ostride, sstride, static_cast<uint32_t>(Sv),
-                            static_cast<uint32_t>(k), nb, true, c->stage_mask.as<uint64_t>() + p0, npat > 1,
-                            c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-  }
-  return AG_RS_OK;
-}
-
-// The decode over the first S bytes of every shard (S % 64 == 0 on the bitsliced paths;
-// shards sstride >= S bytes apart; any alignment).
-int decode_cols(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t sstride, size_t nblocks, uint8_t* orig,
-                size_t ostride, const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres,
-                size_t npat, int mode);
-
-int decode_device_body(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
-                       const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres, size_t npat,
-                       int mode);
-int decode_cols_device_patterns(ag_rs_ctx* c, size_t S, size_t sstride, size_t nblocks, uint8_t* orig,
-                                size_t ostride, const uint8_t* rec, size_t rstride, const uint8_t* opres,
-                                const uint8_t* rpres);
-constexpr int kNotApplicable = -1;
-
-// last_classes counts every pattern of the outermost call: the whole-chunk decode and the
-// tail restride's inner decode of a shard size with S % 64 != 0 add up (reset once per call)
-int decode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
-                  const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres, size_t npat,
-                  int mode) {
-  if (c->decode_depth == 0) std::fill(std::begin(c->last_classes), std::end(c->last_classes), uint64_t{0});
-  ++c->decode_depth;
-  const int st = decode_device_body(c, k, m, S, nblocks, orig, ostride, rec, rstride, opres, rpres, npat, mode);
-  --c->decode_depth;
-  return st;
-}
-
-// The 32-point full-recovery reconstruct (decode class "transform") of shards ending in a split
-// tail chunk: xform8's TAIL variant restores the erased originals, tail included, in place.
-int decode_tail32(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
-                  const uint8_t* rec, size_t rstride, const uint8_t* opres, size_t npat) {
-  if (npat > 1) {
-    bool same = true;
-    for (size_t p = 1; p < npat && same; ++p) same = std::memcmp(opres, opres + p * k, k) == 0;
-    if (same) npat = 1;
-  }
-  std::vector<uint64_t> mask(npat);
-  const uint64_t kmask = (uint64_t{1} << k) - 1;  // k <= 32
-  bool any = false;
-  for (size_t p = 0; p < npat; ++p) {
-    mask[p] = ~pack_flags(opres + p * k, k) & kmask;
-    ++c->last_classes[mask[p] ? 1 : 0];
-    any = any || mask[p];
-  }
-  if (!any) return AG_RS_OK;
-  int st;
-  if (mask != c->mask_host) {
-    AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read mask_host
-    if ((st = c->d_mask.ensure(mask.size() * 8, c->stream))) return st;
-    c->mask_host = mask;
-    AG_HIP(hipMemcpyAsync(c->d_mask.ptr, c->mask_host.data(), mask.size() * 8, hipMemcpyHostToDevice, c->stream));
-  }
-  const size_t cps = padded_shard(S) / 64;
-  ag::XformParams p{};
-  p.in = rec;
-  p.in_block_stride = rstride;
-  p.in_shard_stride = S;
-  p.out = orig;
-  p.out_block_stride = ostride;
-  p.out_shard_stride = S;
-  p.out_mask = c->d_mask.as<uint64_t>();
-  p.pattern_per_block = npat > 1 ? 1u : 0u;
-  p.n_in = static_cast<uint32_t>(m);
-  p.n_out = static_cast<uint32_t>(k);
-  p.chunks_per_shard = static_cast<uint32_t>(cps);
-  p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-  p.tail_bytes = static_cast<uint32_t>(S % 64);
-  p.out_low_half = std::all_of(mask.begin(), mask.end(), [](uint64_t w) { return (w >> 16) == 0; });
-  return launch_tail(c, ag::XformKind::kDecode32, p, false);
-}
-
-int decode_device_body(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
-                       const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres, size_t npat,
-                       int mode) {
-  if (nblocks == 0) return AG_RS_OK;
-  const bool odd = odd_layout(orig, rec, ostride, rstride);
-  if (k <= 64 && (S % 64 != 0 || odd) && S % 2 == 0) {
-    const size_t Sp = padded_shard(S);
-    const int hr = ag::use_high_rate(k, m);
-    const size_t xw = hr == 1 ? next_pow2(next_pow2(m) + k) : 0;
-    if (xform_points(k, m, Sp) || mc_chunk(k, m, Sp) || lowrate_chunk(k, m, Sp) || xw == 32 || xw == 64) {
-      if (odd) return decode_restrided(c, k, m, S, S, 0, nblocks, orig, ostride, rec, rstride, opres, rpres, npat, mode);
-      const size_t full = S / 64 * 64, tail = S - full;
-      // every pattern restores from the full 32-point recovery set (or restores nothing): the
-      // TAIL transform decodes the whole shards, tail included, in place in one launch
-      if (tail >= 16 && xform_points(k, m, Sp) == 32 && m == 32 && mode == AG_RS_DECODE_ANY_K) {
-        bool all_full = true;
-        for (size_t p = 0; p < npat && all_full; ++p) all_full = count_flags(rpres + p * m, m) == m;
-        if (all_full) return decode_tail32(c, k, m, S, nblocks, orig, ostride, rec, rstride, opres, npat);
-      }
-      int st;
-      // per-block 32:32 patterns with lost recovery shards (ANY_K): the per-lane window decode
-      // takes the whole shards, the T-byte tail as one more column (decode_h8 TAIL), no restride
-      if (tail != 0 && npat > 1 && npat == nblocks && k == 32 && m == 32 && hr == 1 && mode == AG_RS_DECODE_ANY_K) {
-        st = decode_cols_device_patterns(c, S, S, nblocks, orig, ostride, rec, rstride, opres, rpres);
-        if (st != kNotApplicable) return st;
-      }
-      if (full && (st = decode_cols(c, k, m, full, S, nblocks, orig, ostride, rec, rstride, opres, rpres, npat, mode)))
-        return st;
-      return decode_restrided(c, k, m, tail, S, full, nblocks, orig, ostride, rec, rstride, opres, rpres, npat, mode);
-    }
-  }
-  return decode_cols(c, k, m, S, S, nblocks, orig, ostride, rec, rstride, opres, rpres, npat, mode);
-}
-
-
-// Per-block patterns of the 32:32 code on tiles that straddle blocks (chunks per shard not a
-// multiple of 64: the follower's slices, tail shreds' whole chunks and their restrided tails),
-// ANY_K, where some recovery shards are lost: the per-lane window decode with its masks built
-// on the device (launch_pipe_patterns, the coder batches' kernel), so the host only packs the
-// presence flags (AVX2) -- the per-pattern classification, window masks and mask compares cost
-// ~25 ns per pattern and call on the host, 3-7 ms per 131 072-block call
-// (profiles/r06_kt_tail_lose4_kernel_stats.csv against the call's wall time).  kNotApplicable
-// when some pattern has its full recovery set and lost data (the transform decodes those) --
-// the host route below takes the call then.
-int decode_cols_device_patterns(ag_rs_ctx* c, size_t S, size_t sstride, size_t nblocks, uint8_t* orig,
-                                size_t ostride, const uint8_t* rec, size_t rstride, const uint8_t* opres,
-                                const uint8_t* rpres) {
-  constexpr size_t k = 32, m = 32, W = 64;
-  // S = 64 C, or 64 C + T with a tail of T >= 16 bytes as the last column (decode_h8 TAIL)
-  const size_t n = nblocks, cps = (S + 63) / 64;
-  int st;
-  if (c->present_ev) AG_HIP(hipEventSynchronize(c->present_ev));  // the previous upload has read h_present
-  else AG_HIP(hipEventCreateWithFlags(&c->present_ev, hipEventDisableTiming));
-  if ((st = c->h_present.ensure(n * 8))) return st;
-  uint64_t* pres = c->h_present.as<uint64_t>();
-  bool full_data = false;
-  (void)pack_present_words(opres, rpres, m, n, pres, &full_data);
-  size_t restore = 0;
-  for (size_t b = 0; b < n; ++b) {
-    const uint64_t w = pres[b];
-    if (__builtin_popcountll(w) < static_cast<int>(k)) return AG_RS_ERR_NOT_ENOUGH_SHARDS;  // nothing launched
-    const bool data_full = (w & 0xFFFFFFFFull) == 0xFFFFFFFFull;
-    if (!data_full && (w >> 32) == 0xFFFFFFFFull) return kNotApplicable;
-    restore += data_full ? 0 : 1;
-  }
-  c->last_classes[0] += n - restore;
-  c->last_classes[3] += restore;
-  if (!restore) return AG_RS_OK;
-  if ((st = c->ensure_tables()) || (st = c->d_present.ensure(n * 8, c->stream)) ||
-      (st = c->d_pipe_few.ensure(n, c->stream)) || (st = c->d_xmask.ensure(3 * n * 8, c->stream)) ||
-      (st = c->d_rows.ensure(n * W * 4, c->stream)))
-    return st;
-  c->xmask_host.clear();  // d_xmask / d_rows no longer hold the host route's cached patterns
-  c->xmask_w = 0;
-  AG_HIP(hipMemcpyAsync(c->d_present.ptr, pres, n * 8, hipMemcpyHostToDevice, c->stream));
-  AG_HIP(hipEventRecord(c->present_ev, c->stream));
-  uint64_t* xm = c->d_xmask.as<uint64_t>();
-  uint32_t* rows = c->d_rows.as<uint32_t>();
-  if (ag::launch_pipe_patterns(c->d_present.as<uint64_t>(), n, xm, c->d_pipe_few.as<uint8_t>(), false, c->stream) !=
-          hipSuccess ||
-      ag::launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), static_cast<uint32_t>(W), c->dtables(), rows, true,
-                             c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  ag::DecodeXParams p{};
-  p.rec = rec;
-  p.rec_block_stride = rstride;
-  p.rec_shard_stride = sstride;
-  p.orig = orig;
-  p.orig_block_stride = ostride;
-  p.orig_shard_stride = sstride;
-  p.pmask = xm + n;
-  p.rows = rows;
-  p.k = static_cast<uint32_t>(k);
-  p.m = static_cast<uint32_t>(m);
-  p.chunk = 32;
-  p.low_rate = 0;
-  p.chunks_per_shard = static_cast<uint32_t>(cps);
-  p.total_columns = static_cast<uint64_t>(n) * cps;
-  p.per_lane = 1;
-  p.rows_w = static_cast<uint32_t>(W);
-  p.any_k = 1;  // launch_pipe_patterns keeps exactly k survivors
-  p.tail_bytes = static_cast<uint32_t>(S % 64);
-  if (ag::launch_decode_x(static_cast<unsigned>(W), 0, p, (p.total_columns + 63) / 64, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  return AG_RS_OK;
-}
-
-int decode_cols(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t sstride, size_t nblocks, uint8_t* orig,
-                size_t ostride, const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres,
-                size_t npat, int mode) {
-  const int hr = ag::use_high_rate(k, m);
-  // one erasure pattern repeated for every block (a repair batch, a uniform loss) is one
-  // pattern: uniform store masks, and the bitsliced kernels regardless of block alignment
-  if (npat > 1) {
-    bool same = true;
-    for (size_t p = 1; p < npat && same; ++p)
-      same = std::memcmp(opres, opres + p * k, k) == 0 && std::memcmp(rpres, rpres + p * m, m) == 0;
-    if (same) npat = 1;
-  }
-  // classify patterns: 0 = nothing to restore, 1 = transform kernel (full recovery set),
-  // 3 = bitsliced general decoder, 2 = table-driven generic kernel.
-  // The transform inverts the encoder only when all N recovery points exist (m == N):
-  // with m < N the points m..N-1 were never stored.
-  std::vector<uint8_t> cls(npat);
-  const bool aligned = true;  // the bitsliced kernels take any alignment (16-byte pieces, unaligned mode)
-  const unsigned npts = xform_points(k, m, S);
-  const bool fast_geo = mode == AG_RS_DECODE_ANY_K && npts != 0 && m == npts && aligned;
-  // decode_x window: HighRate, W = next_pow2(chunk + k) in {32, 64}; or the LowRate
-  // sub-window [0, 64) when next_pow2(k) = 32 (CodingOnly 32:64, PETS 32:33): originals
-  // at 0..k-1, their zero padding k..31 (known zeros, survivors for free), recovery
-  // 0..31 at 32..63.  The LowRate polynomial has degree < 32, so any 32 survivors inside
-  // the window decode it there (ANY_K; patterns with fewer survivors inside take another
-  // path).
-  const bool x_lr = hr == 0 && next_pow2(k) == 32 && mode == AG_RS_DECODE_ANY_K;
-  const size_t xchunk = hr == 1 ? next_pow2(m) : x_lr ? 32 : 0;
-  const size_t xw = hr == 1 ? next_pow2(xchunk + k) : x_lr ? 64 : 0;
-  const size_t xm_rec = hr == 1 ? m : std::min<size_t>(m, 32);  // recovery shards inside the window
-  const size_t cps = S / 64;
-  if (npat > 1 && npat == nblocks && hr == 1 && k == 32 && m == 32 && mode == AG_RS_DECODE_ANY_K && S % 64 == 0 &&
-      cps % 64 != 0 && aligned) {
-    const int st = decode_cols_device_patterns(c, S, sstride, nblocks, orig, ostride, rec, rstride, opres, rpres);
-    if (st != kNotApplicable) return st;
-  }
-  // decode_x: one pattern per tile (single pattern, or tiles that never straddle blocks),
-  // else per-lane patterns (each lane one chunk of one block: the follower's per-slice
-  // patterns on 1 KiB shreds)
-  const bool x_geo = (hr == 1 || x_lr) && S % 64 == 0 && (xw == 32 || xw == 64) && aligned;
-  const bool x_per_lane = npat > 1 && cps % 64 != 0;
-  // decode_syn: the encode_mc geometries (chunk <= 4), any k survivors, same tiling rule
-  const unsigned syn_chunk = mode == AG_RS_DECODE_ANY_K && aligned && (npat == 1 || cps % 64 == 0)
-                                 ? mc_chunk(k, m, S) : 0;
-  std::vector<uint16_t> G;
-  if (syn_chunk) {
-    G.resize(m * k);
-    ag::hr_generator(k, m, G.data());
-  }
-  std::vector<ag::SynPattern> syn;
-  if (syn_chunk) syn.resize(npat);
-  // LowRate (next_pow2(k) = 32): recovery chunk j = FFT_{32(j+1)}(IFFT_0(originals)), so a
-  // fully present chunk inverts through the transform kernel: originals =
-  // FFT_0(IFFT_{32(j+1)}(chunk j)).  ANY_K only (MDS uniqueness), chunks j < 4.
-  const bool lr_geo = mode == AG_RS_DECODE_ANY_K && hr == 0 && next_pow2(k) == 32 && S % 64 == 0 && aligned;
-  std::vector<uint8_t> lr_chunk(npat, 0xFF);
-  bool any_lr = false;
-  // decode_c: the 32-point full-window geometries (HighRate, m = 32, k <= 32) with lost
-  // recovery shards; any k survivors, same tiling rule
-  // (a batch of fewer tiles than CUs is latency-bound -- a single slice per call -- and the
-  // correction's serial SALU phase made one tile a 43 us kernel: those take the window decoder)
-  const uint64_t ncols = static_cast<uint64_t>(nblocks) * cps;
-  const bool corr_geo = mode == AG_RS_DECODE_ANY_K && hr == 1 && m == 32 && k <= 32 && S % 64 == 0 && aligned &&
-                        (npat == 1 || cps % 64 == 0) && ncols < (uint64_t{1} << 31) && ncols >= 64 * 256;
-  // W = 128 windows as two 64-point passes (decode_x16 PASS 1 / 2): the originals in one
-  // window half -- HighRate with next_pow2(m) = 64 (originals at 64..127), LowRate with
-  // next_pow2(k) <= 64 and next_pow2(k) + m in (64, 128] (originals at 0..k-1).  Any k
-  // survivors (exactly k: the codeword is then unique, so the pass split's own erasure set
-  // gives the crate's bytes)
-  const size_t c128 = hr == 1 ? next_pow2(m) : next_pow2(k);
-  const bool x128_geo = S % 64 == 0 && k <= 64 &&
-                        (hr == 1 ? c128 == 64 : (c128 <= 64 && c128 + m > 64 && c128 + m <= 128));
-  bool any_fast = false, any_generic = false, any_x = false, any_syn = false, any_corr = false, any_x128 = false;
-  for (size_t p = 0; p < npat; ++p) {
-    const size_t no = count_flags(opres + p * k, k), nr = count_flags(rpres + p * m, m);
-    if (no + nr < k) return AG_RS_ERR_NOT_ENOUGH_SHARDS;  // nothing launched yet
-    if (no == k) {
-      cls[p] = 0;
-    } else if (fast_geo && nr == m) {
-      cls[p] = 1;
-      any_fast = true;
-    } else if (lr_geo && [&] {
-                 for (size_t j = 0; j < 4 && 32 * (j + 1) <= m; ++j) {
-                   bool full = true;
-                   for (size_t i = 32 * j; i < 32 * (j + 1) && full; ++i) full = rpres[p * m + i] != 0;
-                   if (full) {
-                     lr_chunk[p] = static_cast<uint8_t>(j);
-                     return true;
-                   }
-                 }
-                 return false;
-               }()) {
-      cls[p] = 5;
-      any_lr = true;
-    } else if (syn_chunk && build_syn_pattern(k, m, opres + p * k, rpres + p * m, G.data(), &syn[p])) {
-      cls[p] = 4;
-      any_syn = true;
-    } else if (corr_geo && corr_fits(k, no, nr)) {
-      cls[p] = 6;
-      any_corr = true;
-    } else if (x_geo && (hr == 1 || count_flags(opres + p * k, k) + count_flags(rpres + p * m, xm_rec) >= k)) {
-      cls[p] = 3;
-      any_x = true;
-    } else if (x128_geo && (mode == AG_RS_DECODE_ANY_K || no + nr == k)) {
-      cls[p] = 8;
-      any_x128 = true;
-    } else {
-      cls[p] = 2;
-      any_generic = true;
-    }
-  }
-  for (size_t p = 0; p < npat; ++p) ++c->last_classes[cls[p]];
-  int st;
-  if (any_fast) {
-    // store mask word per pattern: restore original i iff the pattern is fast and i is absent
-    std::vector<uint64_t> mask(npat, 0);
-    const uint64_t kmask = k >= 64 ? ~uint64_t{0} : (uint64_t{1} << k) - 1;  // npts <= 64: k <= 64
-    for (size_t p = 0; p < npat; ++p)
-      if (cls[p] == 1) mask[p] = ~pack_flags(opres + p * k, k) & kmask;
-    // upload only when the pattern set changed (steady-state batches reuse it, no sync)
-    if (mask != c->mask_host) {
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read mask_host
-      if ((st = c->d_mask.ensure(mask.size() * 8, c->stream))) return st;
-      c->mask_host = mask;
-      AG_HIP(hipMemcpyAsync(c->d_mask.ptr, c->mask_host.data(), mask.size() * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    ag::XformParams p{};
-    p.in = rec;
-    p.in_block_stride = rstride;
-    p.in_shard_stride = sstride;
-    p.out = orig;
-    p.out_block_stride = ostride;
-    p.out_shard_stride = sstride;
-    p.out_mask = c->d_mask.as<uint64_t>();
-    p.pattern_per_block = npat > 1 ? 1u : 0u;
-    p.n_in = static_cast<uint32_t>(m);
-    p.n_out = static_cast<uint32_t>(k);
-    p.chunks_per_shard = static_cast<uint32_t>(S / 64);
-    p.total_columns = static_cast<uint64_t>(nblocks) * (S / 64);
-    // all restored originals among shards 0..15: the output-pruned 32-point transform
-    // (64-point: every restored original among shards 0..31, xform_h8's pruned FFT)
-    p.out_low_half = (npts == 32 && std::all_of(mask.begin(), mask.end(), [](uint64_t w) { return (w >> 16) == 0; })) ||
-                     (npts == 64 && std::all_of(mask.begin(), mask.end(), [](uint64_t w) { return (w >> 32) == 0; }));
-    const auto kind = npts == 32 ? ag::XformKind::kDecode32 : ag::XformKind::kDecode64;
-    if (ag::launch_xform(kind, p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  if (any_lr) {
-    // one launch per recovery chunk in use; store masks select that chunk's patterns
-    for (unsigned j = 0; j < 4; ++j) {
-      std::vector<uint64_t> mask(npat, 0);
-      bool used = false;
-      for (size_t p = 0; p < npat; ++p)
-        if (cls[p] == 5 && lr_chunk[p] == j) {
-          used = true;
-          for (size_t i = 0; i < k; ++i)
-            if (!opres[p * k + i]) mask[p] |= uint64_t{1} << i;
-        }
-      if (!used) continue;
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read mask_host
-      if ((st = c->d_mask.ensure(mask.size() * 8, c->stream))) return st;
-      c->mask_host = mask;
-      AG_HIP(hipMemcpyAsync(c->d_mask.ptr, c->mask_host.data(), mask.size() * 8, hipMemcpyHostToDevice, c->stream));
-      ag::XformParams p{};
-      p.in = rec + static_cast<size_t>(32) * j * sstride;
-      p.in_block_stride = rstride;
-      p.in_shard_stride = sstride;
-      p.out = orig;
-      p.out_block_stride = ostride;
-      p.out_shard_stride = sstride;
-      p.out_mask = c->d_mask.as<uint64_t>();
-      p.pattern_per_block = npat > 1 ? 1u : 0u;
-      p.n_in = 32;
-      p.n_out = static_cast<uint32_t>(k);
-      p.chunks_per_shard = static_cast<uint32_t>(S / 64);
-      p.total_columns = static_cast<uint64_t>(nblocks) * (S / 64);
-      if (ag::launch_xform_lowrate_decode(j, p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    }
-  }
-  if (any_syn) {
-    // pattern upload only when (k, m, flags) changed; non-syndrome patterns stay zeroed
-    std::vector<uint8_t> key(16 + npat * (k + m));
-    const uint64_t km[2] = {k, m};
-    std::memcpy(key.data(), km, 16);
-    for (size_t p = 0; p < npat; ++p) {
-      if (cls[p] != 4) continue;
-      std::memcpy(&key[16 + p * (k + m)], opres + p * k, k);
-      std::memcpy(&key[16 + p * (k + m) + k], rpres + p * m, m);
-    }
-    if (key != c->syn_key) {
-      for (size_t p = 0; p < npat; ++p)
-        if (cls[p] != 4) std::memset(&syn[p], 0, sizeof syn[p]);
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read d_syn
-      if ((st = c->d_syn.ensure(npat * sizeof(ag::SynPattern), c->stream))) return st;
-      AG_HIP(hipMemcpy(c->d_syn.ptr, syn.data(), npat * sizeof(ag::SynPattern), hipMemcpyHostToDevice));
-      c->syn_key = key;
-    }
-    ag::DecodeSynParams p{};
-    p.rec = rec;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.orig = orig;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.pat = c->d_syn.as<ag::SynPattern>();
-    p.k = static_cast<uint32_t>(k);
-    p.chunks_per_shard = static_cast<uint32_t>(cps);
-    p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-    if (npat == 1) {
-      p.ntiles = (p.total_columns + 63) / 64;
-    } else {
-      p.per_block = 1;
-      p.tiles_per_block = static_cast<uint32_t>(cps / 64);
-      std::vector<uint32_t> ids;
-      for (size_t b = 0; b < nblocks; ++b)
-        if (cls[b] == 4) ids.push_back(static_cast<uint32_t>(b));
-      if (ids.size() != nblocks) {
-        AG_HIP(hipStreamSynchronize(c->stream));  // a previous id upload may be pending
-        if ((st = c->d_synblocks.ensure(ids.size() * 4, c->stream))) return st;
-        AG_HIP(hipMemcpy(c->d_synblocks.ptr, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-        p.block_ids = c->d_synblocks.as<uint32_t>();
-      }
-      p.ntiles = static_cast<uint64_t>(ids.size()) * p.tiles_per_block;
-    }
-    if (ag::launch_decode_syn(syn_chunk, p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  if (any_corr) {
-    // patterns are built and uploaded only when (k, m, flags) changed
-    std::vector<uint8_t> key(16 + npat * (k + m));
-    const uint64_t km[2] = {k, m};
-    std::memcpy(key.data(), km, 16);
-    for (size_t p = 0; p < npat; ++p) {
-      if (cls[p] != 6) continue;
-      std::memcpy(&key[16 + p * (k + m)], opres + p * k, k);
-      std::memcpy(&key[16 + p * (k + m) + k], rpres + p * m, m);
-    }
-    if (key != c->corr_key) {
-      std::vector<ag::CorrPattern> corr(npat);
-      std::vector<uint32_t> pool;
-      for (size_t p = 0; p < npat; ++p) {
-        if (cls[p] != 6) {
-          std::memset(&corr[p], 0, sizeof corr[p]);
-          continue;
-        }
-        // corr_fits admitted the pattern; the MDS property makes N invertible
-        if (!build_corr_pattern(k, opres + p * k, rpres + p * m, &corr[p], pool)) return AG_RS_ERR_DEVICE;
-      }
-      c->corr_key.clear();
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read d_corr
-      if ((st = c->d_corr.ensure(npat * sizeof(ag::CorrPattern), c->stream))) return st;
-      if ((st = c->d_corrk.ensure(std::max<size_t>(pool.size(), 1) * 4, c->stream))) return st;
-      AG_HIP(hipMemcpy(c->d_corr.ptr, corr.data(), npat * sizeof(ag::CorrPattern), hipMemcpyHostToDevice));
-      if (!pool.empty()) AG_HIP(hipMemcpy(c->d_corrk.ptr, pool.data(), pool.size() * 4, hipMemcpyHostToDevice));
-      c->corr_key = key;
-    }
-    ag::DecodeCParams p{};
-    p.rec = rec;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.orig = orig;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.pat = c->d_corr.as<ag::CorrPattern>();
-    p.kpool = c->d_corrk.as<uint32_t>();
-    p.k = static_cast<uint32_t>(k);
-    p.chunks_per_shard = static_cast<uint32_t>(cps);
-    p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-    if (npat == 1) {
-      p.ntiles = (p.total_columns + 63) / 64;
-    } else {
-      p.per_block = 1;
-      p.tiles_per_block = static_cast<uint32_t>(cps / 64);
-      std::vector<uint32_t> ids;
-      for (size_t b = 0; b < nblocks; ++b)
-        if (cls[b] == 6) ids.push_back(static_cast<uint32_t>(b));
-      if (ids.size() != nblocks) {
-        AG_HIP(hipStreamSynchronize(c->stream));  // a previous id upload may be pending
-        if ((st = c->d_corrblocks.ensure(ids.size() * 4, c->stream))) return st;
-        AG_HIP(hipMemcpy(c->d_corrblocks.ptr, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-        p.block_ids = c->d_corrblocks.as<uint32_t>();
-      }
-      p.ntiles = static_cast<uint64_t>(ids.size()) * p.tiles_per_block;
-    }
-    if (ag::launch_decode_c(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  if (any_x) {
-    if ((st = c->ensure_tables())) return st;
-    // per pattern: [erased (locator) | present (loaded) | restored] position bits
-    std::vector<uint64_t> xm(3 * npat, 0);
-    for (size_t p = 0; p < npat; ++p) {
-      if (cls[p] != 3) continue;
-      uint64_t e, in, out;
-      window64_masks(hr == 1, k, m, xchunk, xm_rec, opres + p * k, rpres + p * m, mode == AG_RS_DECODE_ANY_K, &e, &in,
-                     &out);
-      xm[p] = e;
-      xm[npat + 2 * p] = in;
-      xm[npat + 2 * p + 1] = out;
-    }
-    // polynomial-basis constants (one word per position) for decode_x16 (W = 64) and for
-    // per-lane patterns; bitsliced matrices for decode_x<4>'s wave-uniform four-Russians products
-    const bool poly = xw == 64 || (npat > 1 && x_per_lane);
-    if (xm != c->xmask_host || xw != c->xmask_w || poly != c->xmask_poly) {
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read xmask_host
-      if ((st = c->d_xmask.ensure(xm.size() * 8, c->stream))) return st;
-      if ((st = c->d_rows.ensure(npat * xw * (poly ? 1 : 16) * 4, c->stream))) return st;
-      c->xmask_host = xm;
-      c->xmask_w = xw;
-      c->xmask_poly = poly;
-      AG_HIP(hipMemcpyAsync(c->d_xmask.ptr, c->xmask_host.data(), xm.size() * 8, hipMemcpyHostToDevice, c->stream));
-      const uint64_t* dx = c->d_xmask.as<uint64_t>();
-      if (ag::launch_decode_rows(dx, dx + npat, static_cast<uint32_t>(npat), static_cast<uint32_t>(xw), c->dtables(),
-                                 c->d_rows.as<uint32_t>(), poly, c->stream) != hipSuccess)
-        return AG_RS_ERR_DEVICE;
-    }
-    ag::DecodeXParams p{};
-    p.rec = rec;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.orig = orig;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.pmask = c->d_xmask.as<uint64_t>() + npat;
-    p.rows = c->d_rows.as<uint32_t>();
-    p.k = static_cast<uint32_t>(k);
-    p.m = static_cast<uint32_t>(xm_rec);
-    p.chunk = static_cast<uint32_t>(xchunk);
-    p.low_rate = hr == 1 ? 0u : 1u;
-    p.chunks_per_shard = static_cast<uint32_t>(cps);
-    p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-    p.rows_w = static_cast<uint32_t>(xw);
-    p.any_k = mode == AG_RS_DECODE_ANY_K ? 1u : 0u;
-    uint64_t ntiles;
-    if (npat == 1) {
-      ntiles = (p.total_columns + 63) / 64;
-    } else if (x_per_lane) {
-      p.per_lane = 1;  // lanes of blocks outside class 3 find all-zero masks: no loads, no stores
-      ntiles = (p.total_columns + 63) / 64;
-    } else {
-      p.per_block = 1;
-      p.tiles_per_block = static_cast<uint32_t>(cps / 64);
-      std::vector<uint32_t> ids;
-      for (size_t b = 0; b < nblocks; ++b)
-        if (cls[b] == 3) ids.push_back(static_cast<uint32_t>(b));
-      if (ids.size() != nblocks) {
-        AG_HIP(hipStreamSynchronize(c->stream));  // a previous id upload may be pending
-        if ((st = c->d_xblocks.ensure(ids.size() * 4, c->stream))) return st;
-        AG_HIP(hipMemcpy(c->d_xblocks.ptr, ids.data(), ids.size() * 4, hipMemcpyHostToDevice));
-        p.block_ids = c->d_xblocks.as<uint32_t>();
-      }
-      ntiles = static_cast<uint64_t>(ids.size()) * p.tiles_per_block;
-    }
-    if (ag::launch_decode_x(static_cast<unsigned>(xw), 0, p, ntiles, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  if (any_x128) {
-    if ((st = c->ensure_tables())) return st;
-    // per pattern: m6 = {erased, present, restored} as (positions 0..63, 64..127) pairs, then
-    // the two passes' (present in the loaded half, restored) pairs
-    const size_t oh = hr == 1 ? 1 : 0;  // the output (originals') window half
-    std::vector<uint64_t> xm(10 * npat, 0);
-    for (size_t p = 0; p < npat; ++p) {
-      if (cls[p] != 8) continue;
-      window128_masks(hr == 1, k, m, c128, opres + p * k, rpres + p * m, &xm[10 * p]);
-    }
-    // device: m6 [npat][6], pass-1 pairs [npat][2], pass-2 pairs [npat][2]
-    std::vector<uint64_t> dev(10 * npat);
-    for (size_t p = 0; p < npat; ++p) {
-      for (int i = 0; i < 6; ++i) dev[6 * p + i] = xm[10 * p + i];
-      dev[6 * npat + 2 * p] = xm[10 * p + 6];
-      dev[6 * npat + 2 * p + 1] = xm[10 * p + 7];
-      dev[8 * npat + 2 * p] = xm[10 * p + 8];
-      dev[8 * npat + 2 * p + 1] = xm[10 * p + 9];
-    }
-    // upload (and rebuild the constants) only when the masks changed; the copy is ordered on
-    // the stream and reads the context's own host vector, so nothing waits for it
-    if (dev != c->x128_host) {
-      AG_HIP(hipStreamSynchronize(c->stream));  // a pending upload may still read x128_host
-      if ((st = c->d_x128.ensure(dev.size() * 8, c->stream)) || (st = c->d_rows128.ensure(npat * 128 * 4, c->stream)))
-        return st;
-      c->x128_host = std::move(dev);
-      if (hipMemcpyAsync(c->d_x128.ptr, c->x128_host.data(), c->x128_host.size() * 8, hipMemcpyHostToDevice,
-                         c->stream) != hipSuccess) {
-        c->x128_host.clear();
-        return AG_RS_ERR_DEVICE;
-      }
-      if (ag::launch_decode_rows128(c->d_x128.as<uint64_t>(), static_cast<uint32_t>(npat), c->dtables(),
-                                    c->d_rows128.as<uint32_t>(), c->stream) != hipSuccess)
-        return AG_RS_ERR_DEVICE;
-    }
-    const uint64_t* d6 = c->d_x128.as<uint64_t>();
-    ag::DecodeXParams p{};
-    p.rec = rec;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.orig = orig;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.rows = c->d_rows128.as<uint32_t>();
-    p.rows_w = 128;
-    p.k = static_cast<uint32_t>(k);
-    p.m = static_cast<uint32_t>(m);
-    p.chunk = static_cast<uint32_t>(c128);
-    p.low_rate = hr == 1 ? 0u : 1u;
-    p.chunks_per_shard = static_cast<uint32_t>(cps);
-    p.total_columns = static_cast<uint64_t>(nblocks) * cps;
-    uint64_t ntiles;
-    std::vector<uint32_t> ids;
-    if (npat == 1) {
-      ntiles = (p.total_columns + 63) / 64;
-    } else if (x_per_lane) {
-      p.per_lane = 1;  // lanes of blocks outside class 8 find all-zero masks: no loads, no stores
-      ntiles = (p.total_columns + 63) / 64;
-    } else {
-      p.per_block = 1;
-      p.tiles_per_block = static_cast<uint32_t>(cps / 64);
-      for (size_t b = 0; b < nblocks; ++b)
-        if (cls[b] == 8) ids.push_back(static_cast<uint32_t>(b));
-      // count before the upload below moves `ids` into the context
-      ntiles = static_cast<uint64_t>(ids.size()) * p.tiles_per_block;
-      if (ids.size() != nblocks) {
-        AG_HIP(hipStreamSynchronize(c->stream));  // a pending id upload may still read x128_ids
-        if ((st = c->d_xblocks.ensure(ids.size() * 4, c->stream))) return st;
-        c->x128_ids = std::move(ids);
-        AG_HIP(hipMemcpyAsync(c->d_xblocks.ptr, c->x128_ids.data(), c->x128_ids.size() * 4, hipMemcpyHostToDevice,
-                              c->stream));
-        p.block_ids = c->d_xblocks.as<uint32_t>();
-      }
-    }
-    // recovery shards beyond the window half the kernel loads are addressed from p.rec with
-    // the window position; launch_decode_x checks the geometry
-    p.m = static_cast<uint32_t>(std::min<size_t>(m, p.chunk));
-    for (int pass = 1; pass <= 2; ++pass) {
-      p.pmask = d6 + (pass == 1 ? 6 : 8) * npat;
-      if (ag::launch_decode_x(128, pass, p, ntiles, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    }
-  }
-  if (!any_generic) return AG_RS_OK;
-
-  if ((st = c->ensure_tables())) return st;
-  const size_t chunk = hr ? next_pow2(m) : next_pow2(k);
-  const size_t end = chunk + (hr ? k : m);
-  const size_t W = next_pow2(end);
-  // erasure flags per pattern over the transform window (crate decoder_high/low.rs)
-  std::vector<uint8_t> erased(npat * W, 0);
-  for (size_t p = 0; p < npat; ++p) {
-    if (cls[p] != 2) continue;
-    uint8_t* e = &erased[p * W];
-    const size_t opos = hr ? chunk : 0, rpos = hr ? 0 : chunk;
-    for (size_t i = 0; i < k; ++i) e[opos + i] = opres[p * k + i] ? 0 : 1;
-    for (size_t i = 0; i < m; ++i) e[rpos + i] = rpres[p * m + i] ? 0 : 1;
-    if (hr) {
-      for (size_t i = m; i < chunk; ++i) e[i] = 1;  // virtual recovery points
-    } else {
-      for (size_t i = end; i < W; ++i) e[i] = 1;  // beyond the recovery block
-    }
-  }
-  // per-pattern device copies of the present flags and erasures
-  const size_t flag_bytes = npat * (k + m) + erased.size();
-  if ((st = c->d_flags.ensure(flag_bytes, c->stream))) return st;
-  if ((st = c->d_loc.ensure(npat * W * 2, c->stream))) return st;
-  std::vector<uint8_t> hostflags(flag_bytes);
-  std::memcpy(hostflags.data(), opres, npat * k);
-  std::memcpy(hostflags.data() + npat * k, rpres, npat * m);
-  std::memcpy(hostflags.data() + npat * (k + m), erased.data(), erased.size());
-  uint8_t* dflags = c->d_flags.as<uint8_t>();
-  AG_HIP(hipMemcpyAsync(dflags, hostflags.data(), flag_bytes, hipMemcpyHostToDevice, c->stream));
-  if (ag::launch_locator(dflags + npat * (k + m), static_cast<uint32_t>(npat), static_cast<uint32_t>(W),
-                         hr ? 65536u : static_cast<uint32_t>(end), c->d_log_walsh.as<uint16_t>(),
-                         c->d_loc.as<uint16_t>(), c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  // blocks handled by the generic kernel
-  std::vector<uint32_t> ids;
-  if (npat > 1) {
-    for (size_t b = 0; b < nblocks; ++b)
-      if (cls[b] == 2) ids.push_back(static_cast<uint32_t>(b));
-    if ((st = c->d_blocks.ensure(ids.size() * 4, c->stream))) return st;
-    AG_HIP(hipMemcpyAsync(c->d_blocks.ptr, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->stream));
-  }
-  const size_t ngen = npat > 1 ? ids.size() : nblocks;
-  const size_t nsym = S / 2;
-  const size_t per_block = W * nsym * 2;
-  const size_t per_launch = std::max<size_t>(1, kGenericScratchBytes / per_block);
-  if ((st = c->scratch.ensure(std::min(per_launch, ngen) * per_block, c->stream))) return st;
-  for (size_t b0 = 0; b0 < ngen; b0 += per_launch) {
-    ag::GenericDecodeParams p{};
-    p.orig = orig;
-    p.orig_block_stride = ostride;
-    p.orig_shard_stride = sstride;
-    p.rec = rec;
-    p.rec_block_stride = rstride;
-    p.rec_shard_stride = sstride;
-    p.orig_present = dflags;
-    p.rec_present = dflags + npat * k;
-    p.pattern_per_block = npat > 1 ? 1u : 0u;
-    p.block_ids = npat > 1 ? c->d_blocks.as<uint32_t>() + b0 : nullptr;
-    p.block_base = npat > 1 ? 0 : b0;
-    p.loc = c->d_loc.as<uint16_t>();
-    p.k = static_cast<uint32_t>(k);
-    p.m = static_cast<uint32_t>(m);
-    p.high_rate = static_cast<uint32_t>(hr);
-    p.chunk = static_cast<uint32_t>(chunk);
-    p.end = static_cast<uint32_t>(end);
-    p.W = static_cast<uint32_t>(W);
-    p.shard_bytes = static_cast<uint32_t>(S);
-    p.nsym = static_cast<uint32_t>(nsym);
-    p.nblocks = std::min(per_launch, ngen - b0);
-    p.scratch = c->scratch.as<uint16_t>();
-    p.t = c->dtables();
-    if (ag::launch_generic_decode(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  // host vectors above are read by async copies: finish before they go out of scope
-  AG_HIP(hipStreamSynchronize(c->stream));
-  return AG_RS_OK;
-}
 
 }  // namespace
 
@@ -1095,12 +116,7 @@ static int switch_stream(ag_rs_ctx* c, hipStream_t s) {
   if (s == c->stream) return AG_RS_OK;
   if (c->enter() || hipStreamSynchronize(c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   c->stream = s;
-  c->mask_host.clear();
-  c->stage_mask_host.clear();
-  c->xmask_host.clear();
-  c->x128_host.clear();
-  c->syn_key.clear();
-  c->corr_key.clear();
+  c->forget_uploads();
   return AG_RS_OK;
 }
 
@@ -1128,9 +144,7 @@ int ag_rs_use_high_rate(size_t k, size_t m) {
 }
 
 // Test aid (not in the public header's contract): patterns per decoder class in the last
-// decode on this context -- 0 nothing to restore, 1 full-recovery transform, 2 table-driven
-// generic, 3 W <= 64 window (decode_x / decode_x16), 4 syndrome, 5 LowRate chunk transform,
-// 6 correction (decode_c), 8 W = 128 two-pass window.
+// decode on this context, indexed by ag::DecodeClass (rs_patterns.hpp).
 int ag_rs_internal_last_decode_classes(ag_rs_ctx* c, uint64_t* out16) {
   if (!c || !out16) return AG_RS_ERR_INVALID_ARGUMENT;
   std::memcpy(out16, c->last_classes, sizeof c->last_classes);
@@ -1257,8 +271,7 @@ int ag_rs_decode_batch(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblock
     for (size_t i = 0; i < m; ++i) nr += rpres[i] != 0;
     for (size_t i = 0; i < k; ++i) no += opres[i] != 0;
     if (no == k) return AG_RS_OK;  // nothing to restore
-    const unsigned npts = xform_points(k, m, S);
-    need_orig = !(mode == AG_RS_DECODE_ANY_K && npts && m == npts && nr == m);
+    need_orig = !ag::transform_restores(k, m, S, mode, nr);
   }
   size_t g = 0;
   for (size_t b0 = 0; b0 < nblocks; b0 += group, ++g) {
@@ -1885,7 +898,7 @@ int run_one_decode(ag_rs_ctx* c, size_t k, size_t m, size_t S, PinBuf& pin, cons
     for (size_t i = 0; i < k; ++i)
       if (!opres[i]) mask |= uint64_t{1} << i;
     std::fill(std::begin(c->last_classes), std::end(c->last_classes), uint64_t{0});
-    ++c->last_classes[mask ? 1 : 0];  // "transform" (or "none")
+    ++c->last_classes[mask ? ag::kTransform : ag::kNone];
     if (mask && (st = server_job(c, (mask >> 16) ? ag::kJobDecode32 : ag::kJobDecode32Half,
                                  one_tile(pd + ob, rb, pd, ob, S), mask, pin)))
       return st;
@@ -1925,7 +938,7 @@ int run_one_decode(ag_rs_ctx* c, size_t k, size_t m, size_t S, PinBuf& pin, cons
     dp.fuse = 1;
     dp.tail_bytes = static_cast<uint32_t>(S % 64);
     std::fill(std::begin(c->last_classes), std::end(c->last_classes), uint64_t{0});
-    ++c->last_classes[9];  // "server_window64"
+    ++c->last_classes[ag::kServerWindow64];
     if ((st = server_job(c, ag::kJobDecodePk, ag::XformParams{}, pres, pin, &dp))) return st;
     if (coding_src) *coding_src = pin.as<uint8_t>() + ob;  // the whole coding set, in place
     return AG_RS_OK;
@@ -2358,52 +1371,6 @@ int ag_rs_coder_shred_batch(ag_rs_ctx* c, size_t m, size_t n, size_t S, const ui
 }
 
 namespace {
-// Per-slice present words of ag_rs_coder_deshred_batch's device-pattern path: word 0 = data
-// flags | coding 0..31 << 32 (and word 1 = coding 32..63 when m = 64).  Returns whether any
-// slice keeps more than 32 shreds.  The flag bytes are 4 MiB per 65 536 slices: compared 32
-// at a time with AVX2 where the host has it (the 8-byte multiply trick of pack_flags took
-// ~0.5 ms of the call).
-__attribute__((target("avx2"))) uint32_t nonzero_mask32_avx2(const uint8_t* f) {
-  const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(f));
-  return ~static_cast<uint32_t>(_mm256_movemask_epi8(_mm256_cmpeq_epi8(x, _mm256_setzero_si256())));
-}
-// (a macro body, not a template: this part of the file has C linkage)
-#define AG_PACK_PRESENT(MASK32)                                                   \
-  const size_t wps = m == kDataShreds ? 1 : 2;                                    \
-  bool surplus = false, full_data = false;                                        \
-  for (size_t b = 0; b < n; ++b) {                                                \
-    uint64_t* q = pres + wps * b;                                                 \
-    q[0] = uint64_t{MASK32(dpres + b * kDataShreds)} | (uint64_t{MASK32(cpres + b * m)} << 32); \
-    int cnt = __builtin_popcountll(q[0]);                                         \
-    if (wps == 2) {                                                               \
-      q[1] = m == 2 * kDataShreds ? MASK32(cpres + b * m + 32)                    \
-                                  : pack_flags(cpres + b * m + 32, m - 32);       \
-      cnt += __builtin_popcountll(q[1]);                                          \
-    }                                                                             \
-    surplus |= cnt > static_cast<int>(kDataShreds);                               \
-    full_data |= (q[0] & 0xFFFFFFFFull) == 0xFFFFFFFFull;                         \
-  }                                                                               \
-  *any_full_data = full_data;                                                     \
-  return surplus;
-__attribute__((target("avx2"))) bool pack_present_avx2(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n,
-                                                       uint64_t* pres, bool* any_full_data) {
-  AG_PACK_PRESENT(nonzero_mask32_avx2)
-}
-uint32_t nonzero_mask32(const uint8_t* f) { return static_cast<uint32_t>(pack_flags(f, 32)); }
-bool pack_present_scalar(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n, uint64_t* pres,
-                         bool* any_full_data) {
-  AG_PACK_PRESENT(nonzero_mask32)
-}
-#undef AG_PACK_PRESENT
-// *any_full_data: some slice holds every data shred (its decode is skipped, so its absent
-// coding shreds come from the re-encode)
-bool pack_present_words(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n, uint64_t* pres,
-                        bool* any_full_data) {
-  static const bool avx2 = __builtin_cpu_supports("avx2");
-  return avx2 ? pack_present_avx2(dpres, cpres, m, n, pres, any_full_data)
-              : pack_present_scalar(dpres, cpres, m, n, pres, any_full_data);
-}
-
 // ag_rs_coder_deshred_batch when every slice has the same present shreds (pattern = slice 0's).
 int coder_deshred_uniform(ag_rs_ctx* c, size_t m, size_t n, size_t S, uint8_t* cw, size_t cw_stride,
                           const uint8_t* dpres, const uint8_t* cpres, int mode, int64_t* out) {
@@ -2979,9 +1946,9 @@ int pipe_coder_reserve(ag_rs_ctx* c, size_t ntot, size_t m) {
       (st = c->d_pipe_mask.ensure(8 * ntot, c->stream)) || (st = c->d_strip.ensure(8 * ntot, c->stream)))
     return st;
   if (m > kDataShreds)
-    return (st = c->d_x128.ensure(10 * ntot * 8, c->stream)) ? st : c->d_rows128.ensure(ntot * 128 * 4, c->stream);
-  if ((st = c->d_xmask.ensure(3 * ntot * 8, c->stream)) || (st = c->d_rows.ensure(ntot * 64 * 4, c->stream))) return st;
-  c->xmask_host.clear();  // d_xmask / d_rows no longer hold decode_device's cached patterns
+    return (st = c->x128.dev.ensure(10 * ntot * 8, c->stream)) ? st : c->d_rows128.ensure(ntot * 128 * 4, c->stream);
+  if ((st = c->xmask.dev.ensure(3 * ntot * 8, c->stream)) || (st = c->d_rows.ensure(ntot * 64 * 4, c->stream))) return st;
+  c->xmask.key.clear();  // xmask.dev / d_rows no longer hold decode_device's cached patterns
   c->xmask_w = 0;
   return AG_RS_OK;
 }
@@ -2995,7 +1962,7 @@ int pipe_coder_enqueue_lowrate(ag_rs_ctx* c, size_t s0, size_t n, size_t S, uint
                                const uint64_t* d_present, size_t m) {
   constexpr size_t k = kDataShreds;
   const size_t cps = S / 64;
-  uint64_t* xm = c->d_x128.as<uint64_t>() + 10 * s0;
+  uint64_t* xm = c->x128.dev.as<uint64_t>() + 10 * s0;
   uint32_t* rows = c->d_rows128.as<uint32_t>() + 128 * s0;
   uint8_t* few = c->d_pipe_few.as<uint8_t>() + s0;
   uint64_t* mask = c->d_pipe_mask.as<uint64_t>() + s0;
@@ -3060,7 +2027,7 @@ int pipe_coder_enqueue(ag_rs_ctx* c, size_t s0, size_t n, size_t S, uint8_t* cw,
   if (n == 0) return AG_RS_OK;
   if (m > kDataShreds) return pipe_coder_enqueue_lowrate(c, s0, n, S, cw, cw_stride, d_present, m);
   constexpr size_t W = 64;
-  uint64_t* xm = c->d_xmask.as<uint64_t>() + 3 * s0;
+  uint64_t* xm = c->xmask.dev.as<uint64_t>() + 3 * s0;
   uint32_t* rows = c->d_rows.as<uint32_t>() + W * s0;
   uint8_t* few = c->d_pipe_few.as<uint8_t>() + s0;
   uint64_t* mask = c->d_pipe_mask.as<uint64_t>() + s0;
@@ -3298,7 +2265,7 @@ int ag_rs_coder_deshred_batch_var(ag_rs_ctx* c, size_t m, size_t n, const uint32
   // not depend on S), the window decode with the fused coding restore, the strip, the store
   // masks, the re-encode
   if ((st = pipe_coder_reserve(c, n, kDataShreds))) return st;
-  uint64_t* xm = c->d_xmask.as<uint64_t>();
+  uint64_t* xm = c->xmask.dev.as<uint64_t>();
   uint32_t* rows = c->d_rows.as<uint32_t>();
   uint8_t* few = c->d_pipe_few.as<uint8_t>();
   uint64_t* mask = c->d_pipe_mask.as<uint64_t>();

@@ -1,7 +1,7 @@
 // The device context behind the C ABI (include/alpenglow_rs.h) and the helpers the host
-// translation units share: rs_api.cpp (which defines them) and shredder_api.cpp.  Internal:
-// not installed, included only by the host .cpp files; nothing here is exported from the
-// shared object.
+// translation units share: rs_api.cpp (the C ABI), rs_dispatch.cpp (the batch encode / decode
+// dispatch) and shredder_api.cpp.  Internal: not installed, included only by the host .cpp
+// files; nothing here is exported from the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -86,11 +86,42 @@ struct PinBuf {
   }
 };
 
+// "Upload only when the pattern set changed": a device buffer and the host key of what it
+// holds.  While the key matches (steady-state batches) a call neither copies nor waits.
+template <typename K>
+struct UploadCache {
+  std::vector<K> key;  // what `dev` holds; the context-owned source of upload()'s asynchronous copy
+  DevBuf dev;
+  bool holds(const std::vector<K>& k) const { return k == key; }
+  // A miss: one stream synchronisation (a pending upload may still read `key`, queued kernels
+  // `dev`), then `dev` grown to `bytes`.  The key is dropped -- every key has at least one
+  // entry, so it matches nothing until the caller has filled `dev` and set it again.
+  int renew(size_t bytes, hipStream_t stream) {
+    AG_HIP(hipStreamSynchronize(stream));
+    key.clear();
+    return dev.ensure(bytes, stream);
+  }
+  // The key is the uploaded data: copied on the stream from the cache's own vector.
+  int upload(std::vector<K>&& words, hipStream_t stream) {
+    key = std::move(words);
+    if (hipMemcpyAsync(dev.ptr, key.data(), key.size() * sizeof(K), hipMemcpyHostToDevice, stream) == hipSuccess)
+      return AG_RS_OK;
+    key.clear();
+    return AG_RS_ERR_DEVICE;
+  }
+  int put(std::vector<K>&& words, hipStream_t stream) {
+    if (holds(words)) return AG_RS_OK;
+    const int st = renew(words.size() * sizeof(K), stream);
+    return st ? st : upload(std::move(words), stream);
+  }
+};
+
 }  // namespace host
 }  // namespace ag
 
 using ag::host::DevBuf;
 using ag::host::PinBuf;
+using ag::host::UploadCache;
 
 struct ag_rs_ctx {
   int device = 0;
@@ -99,15 +130,26 @@ struct ag_rs_ctx {
   bool tables_ready = false;
   DevBuf d_exp, d_log, d_skew, d_log_walsh;
   DevBuf scratch;                         // generic-kernel work rows
-  DevBuf d_flags, d_loc, d_blocks, d_mask;  // decode bookkeeping
-  DevBuf d_xmask, d_rows, d_xblocks;        // bitsliced general decode: masks, matrices
-  DevBuf d_x128, d_rows128;                 // W = 128 two-pass decode: masks, constants
-  uint64_t last_classes[16] = {};           // patterns per decoder class of the last decode call
+  DevBuf d_flags, d_loc, d_blocks;          // generic decode: flags, locators, block ids
+  // pattern uploads of the decoder classes (rs_dispatch.cpp), each cache with what is derived from it
+  UploadCache<uint64_t> mask;               // store-mask words of the transform launches
+  UploadCache<uint64_t> stage_mask;         // restride store / pack masks (sizes not whole 64-byte chunks)
+  UploadCache<uint64_t> xmask;              // W <= 64 window masks, for W = xmask_w
+  size_t xmask_w = 0;
+  bool xmask_poly = false;                  // d_rows holds polynomial-basis constants (per-lane)
+  DevBuf d_rows, d_xblocks;                 // their constants / matrices; window block ids (W = 128 too)
+  UploadCache<uint64_t> x128;               // W = 128 two-pass masks
+  DevBuf d_rows128;                         // their constants
+  std::vector<uint32_t> x128_ids;           // host source of the W = 128 block-id upload (d_xblocks)
+  UploadCache<uint8_t> syn;                 // syndrome patterns, key (k, m, present flags)
+  DevBuf d_synblocks;                       // their block ids
+  UploadCache<uint8_t> corr;                // correction patterns, key (k, m, present flags)
+  DevBuf d_corrk, d_corrblocks;             // their K picks, block ids
+  static constexpr int kClassSlots = 16;    // the test aid's out16: one counter per ag::DecodeClass value
+  uint64_t last_classes[kClassSlots] = {};  // patterns per decoder class of the last decode call
   int decode_depth = 0;                     // decode_device nesting (tail restrides decode inside)
   uint32_t last_encode_kernels = 0;         // EncodeKernelBit of the last ag_rs_encode_batch / coder deshred batch
   uint32_t last_window_kernels = 0;         // DecodeXKernelBit of the last coder deshred batch's window decode
-  DevBuf d_syn, d_synblocks;                // syndrome decoder: patterns, block ids
-  DevBuf d_corr, d_corrk, d_corrblocks;     // correction decoder: patterns, K picks, block ids
   DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
   DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
   uint32_t last_merkle_kernels = 0;         // MerkleLeafKernelBit of the last Merkle build's leaf kernel
@@ -122,7 +164,7 @@ struct ag_rs_ctx {
   hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
   hipEvent_t side_fork = nullptr, side_join = nullptr;
   DevBuf d_slice_meta;                           // slice framing / parsing metadata
-  DevBuf stage_pad, stage_mask;                  // restrided shards (sizes not whole 64-byte chunks)
+  DevBuf stage_pad;                              // restrided shards (sizes not whole 64-byte chunks)
   DevBuf d_lens, d_strip;                   // coder batches: payload lengths, strip results
   DevBuf d_reenc_mask;                      // uniform coder deshreds: the re-encode's store mask word
   DevBuf d_pipe_few, d_pipe_mask;           // composed deshred: too-few flags, re-encode store masks
@@ -155,15 +197,16 @@ struct ag_rs_ctx {
   bool fail_next_server_job = false;  // test aid: the next server job takes the timeout path
   uint64_t server_jobs[4] = {};        // jobs posted per LatencyJob kind (test aid)
   std::vector<PinBuf> abandoned_pins;  // staging a timed-out job named (freed once the server is gone)
-  std::vector<uint64_t> mask_host;        // last store-mask words uploaded to d_mask
-  std::vector<uint64_t> stage_mask_host;  // last restride masks uploaded to stage_mask
-  std::vector<uint64_t> xmask_host;       // last general-decode masks (d_xmask), W = xmask_w
-  size_t xmask_w = 0;
-  bool xmask_poly = false;                // d_rows holds polynomial-basis constants (per-lane)
-  std::vector<uint8_t> syn_key;             // (k, m, present flags) of the patterns in d_syn
-  std::vector<uint8_t> corr_key;            // (k, m, present flags) of the patterns in d_corr
-  std::vector<uint64_t> x128_host;          // last W = 128 masks uploaded to d_x128
-  std::vector<uint32_t> x128_ids;           // their per-block ids (d_xblocks)
+
+  // A stream switch forgets the pattern uploads: their copies were ordered on the old stream.
+  void forget_uploads() {
+    mask.key.clear();
+    stage_mask.key.clear();
+    xmask.key.clear();
+    x128.key.clear();
+    syn.key.clear();
+    corr.key.clear();
+  }
 
   int enter() { return hipSetDevice(device) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE; }
 
@@ -273,8 +316,9 @@ struct ag_rs_ctx {
       (void)hipStreamDestroy(h2d);
       (void)hipStreamDestroy(d2h);
     }
-    for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &d_mask,
-                      &d_xmask, &d_rows, &d_xblocks, &d_x128, &d_rows128, &d_syn, &d_synblocks, &d_corr, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_pad, &stage_mask, &d_slice_meta, &one_in,
+    for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &mask.dev,
+                      &stage_mask.dev, &xmask.dev, &d_rows, &d_xblocks, &x128.dev, &d_rows128, &syn.dev, &d_synblocks,
+                      &corr.dev, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_pad, &d_slice_meta, &one_in,
                       &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta, &d_leaf_sizes})
       b->release();
     for (DevBuf& b : pipe) b.release();
@@ -305,14 +349,23 @@ struct ag_rs_ctx {
   }
 };
 
-// The helpers the composed shredders (shredder_api.cpp) call in rs_api.cpp, where each is
-// defined and documented.
+// What the host translation units call in each other; each is documented where it is defined.
 namespace ag {
 namespace host __attribute__((visibility("hidden"))) {
+
+// rs_dispatch.cpp: the batch encode / decode over device memory
+int check_geometry(size_t k, size_t m, size_t S);
+bool odd_layout(const void* a, const void* b, size_t sa, size_t sb);
+int encode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, const uint8_t* orig, size_t ostride,
+                  uint8_t* rec, size_t rstride);
+int decode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, uint8_t* orig, size_t ostride,
+                  const uint8_t* rec, size_t rstride, const uint8_t* opres, const uint8_t* rpres, size_t npat,
+                  int mode);
 
 constexpr size_t kDataShreds = AG_RS_DATA_SHREDS;
 constexpr size_t kMaxPayload = kDataShreds * AG_RS_MAX_DATA_PER_SHRED - 1;
 
+// rs_api.cpp: what the composed shredders (shredder_api.cpp) call
 int ensure_empty_roots(ag_rs_ctx* c);
 int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
                       size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,

@@ -4,6 +4,8 @@
 // correction tables are this build's own decoders.
 #include "rs_patterns.hpp"
 
+#include <immintrin.h>
+
 #include <algorithm>
 
 #include "gf16.hpp"
@@ -298,6 +300,155 @@ void window128_masks(bool hr, size_t k, size_t m, size_t c128, const uint8_t* op
   q[7] = out[oh];
   q[8] = in[oh];      // pass 2: the output half's inputs
   q[9] = out[oh];
+}
+
+namespace {
+// The flag bytes are 4 MiB per 65 536 slices: compared 32 at a time with AVX2 where the host
+// has it (the 8-byte multiply trick of pack_flags took ~0.5 ms of the call).
+__attribute__((target("avx2"))) inline uint32_t nonzero_mask32_avx2(const uint8_t* f) {
+  const __m256i x = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(f));
+  return ~static_cast<uint32_t>(_mm256_movemask_epi8(_mm256_cmpeq_epi8(x, _mm256_setzero_si256())));
+}
+inline uint32_t nonzero_mask32(const uint8_t* f) { return static_cast<uint32_t>(pack_flags(f, 32)); }
+
+// (always inlined: the AVX2 instance has to become part of its target("avx2") caller)
+template <uint32_t (*Mask32)(const uint8_t*)>
+__attribute__((always_inline)) inline bool pack_present(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n,
+                                                        uint64_t* pres, bool* any_full_data) {
+  const size_t wps = m == 32 ? 1 : 2;
+  bool surplus = false, full_data = false;
+  for (size_t b = 0; b < n; ++b) {
+    uint64_t* q = pres + wps * b;
+    q[0] = uint64_t{Mask32(dpres + b * 32)} | (uint64_t{Mask32(cpres + b * m)} << 32);
+    int cnt = __builtin_popcountll(q[0]);
+    if (wps == 2) {
+      q[1] = m == 64 ? Mask32(cpres + b * m + 32) : pack_flags(cpres + b * m + 32, m - 32);
+      cnt += __builtin_popcountll(q[1]);
+    }
+    surplus |= cnt > 32;
+    full_data |= (q[0] & 0xFFFFFFFFull) == 0xFFFFFFFFull;
+  }
+  *any_full_data = full_data;
+  return surplus;
+}
+__attribute__((target("avx2"))) bool pack_present_avx2(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n,
+                                                       uint64_t* pres, bool* any_full_data) {
+  return pack_present<nonzero_mask32_avx2>(dpres, cpres, m, n, pres, any_full_data);
+}
+}  // namespace
+
+bool pack_present_words(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n, uint64_t* pres,
+                        bool* any_full_data) {
+  static const bool avx2 = __builtin_cpu_supports("avx2");
+  return avx2 ? pack_present_avx2(dpres, cpres, m, n, pres, any_full_data)
+              : pack_present<nonzero_mask32>(dpres, cpres, m, n, pres, any_full_data);
+}
+
+bool patterns_equal(size_t k, size_t m, size_t npat, const uint8_t* opres, const uint8_t* rpres) {
+  for (size_t p = 1; p < npat; ++p)
+    if (std::memcmp(opres, opres + p * k, k) != 0 || std::memcmp(rpres, rpres + p * m, m) != 0) return false;
+  return true;
+}
+
+DecodePlan classify_patterns(size_t k, size_t m, size_t S, size_t nblocks, size_t npat, int mode,
+                             const uint8_t* opres, const uint8_t* rpres) {
+  DecodePlan pl;
+  if (npat > 1 && patterns_equal(k, m, npat, opres, rpres)) npat = 1;
+  const bool any_k = mode == AG_RS_DECODE_ANY_K;
+  const int hr = use_high_rate(k, m);
+  const size_t cps = S / 64;
+  const bool chunks = S % 64 == 0;  // the bitsliced kernels take whole 64-byte chunks (any alignment)
+  // one pattern per tile (a single pattern, or tiles that never straddle blocks), the rule of
+  // the syndrome and correction decoders; the window decoders also take per-lane patterns
+  const bool tile_patterns = npat == 1 || cps % 64 == 0;
+  pl.npat = npat;
+  pl.hr = hr;
+  pl.cps = cps;
+  pl.npts = xform_points(k, m, S);
+  pl.per_lane = npat > 1 && cps % 64 != 0;
+  // decode_x window: HighRate, W = next_pow2(chunk + k) in {32, 64}; or the LowRate
+  // sub-window [0, 64) when next_pow2(k) = 32 (CodingOnly 32:64, PETS 32:33): originals
+  // at 0..k-1, their zero padding k..31 (known zeros, survivors for free), recovery
+  // 0..31 at 32..63.  The LowRate polynomial has degree < 32, so any 32 survivors inside
+  // the window decode it there (ANY_K; patterns with fewer survivors inside take another
+  // path).
+  const bool x_lr = hr == 0 && next_pow2(k) == 32 && any_k;
+  pl.xchunk = hr == 1 ? next_pow2(m) : x_lr ? 32 : 0;
+  pl.xw = hr == 1 ? next_pow2(pl.xchunk + k) : x_lr ? 64 : 0;
+  pl.xm_rec = hr == 1 ? m : std::min<size_t>(m, 32);
+  const bool x_geo = (hr == 1 || x_lr) && chunks && (pl.xw == 32 || pl.xw == 64);
+  // decode_syn: the encode_mc geometries (chunk <= 4), any k survivors
+  pl.syn_chunk = any_k && tile_patterns ? mc_chunk(k, m, S) : 0;
+  std::vector<uint16_t> G;
+  if (pl.syn_chunk) {
+    G.resize(m * k);
+    hr_generator(k, m, G.data());
+    pl.syn.resize(npat);
+  }
+  // LowRate (next_pow2(k) = 32): recovery chunk j = FFT_{32(j+1)}(IFFT_0(originals)), so a
+  // fully present chunk inverts through the transform kernel: originals =
+  // FFT_0(IFFT_{32(j+1)}(chunk j)).  ANY_K only (MDS uniqueness), chunks j < 4.
+  const bool lr_geo = any_k && hr == 0 && next_pow2(k) == 32 && chunks;
+  if (lr_geo) pl.lr_chunk.assign(npat, 0xFF);
+  // decode_c: the 32-point full-window geometries (HighRate, m = 32, k <= 32) with lost
+  // recovery shards; any k survivors
+  // (a batch of fewer tiles than CUs is latency-bound -- a single slice per call -- and the
+  // correction's serial SALU phase made one tile a 43 us kernel: those take the window decoder)
+  const uint64_t ncols = static_cast<uint64_t>(nblocks) * cps;
+  const bool corr_geo = any_k && hr == 1 && m == 32 && k <= 32 && chunks && tile_patterns &&
+                        ncols < (uint64_t{1} << 31) && ncols >= 64 * 256;
+  // W = 128 windows as two 64-point passes (decode_x16 PASS 1 / 2): the originals in one
+  // window half -- HighRate with next_pow2(m) = 64 (originals at 64..127), LowRate with
+  // next_pow2(k) <= 64 and next_pow2(k) + m in (64, 128] (originals at 0..k-1).  Any k
+  // survivors (exactly k: the codeword is then unique, so the pass split's own erasure set
+  // gives the crate's bytes)
+  pl.c128 = hr == 1 ? next_pow2(m) : next_pow2(k);
+  const bool x128_geo = chunks && k <= 64 &&
+                        (hr == 1 ? pl.c128 == 64 : (pl.c128 <= 64 && pl.c128 + m > 64 && pl.c128 + m <= 128));
+  // the first fully present 32-shard recovery chunk of a pattern, or 0xFF
+  auto full_chunk = [&](const uint8_t* rp) -> uint8_t {
+    for (size_t j = 0; j < 4 && 32 * (j + 1) <= m; ++j)
+      if (pack_flags(rp + 32 * j, 32) == 0xFFFFFFFFull) return static_cast<uint8_t>(j);
+    return 0xFF;
+  };
+  // kSyndrome patterns are built here; a refused pattern's partial fill is zeroed again
+  auto syn_fits = [&](size_t p, const uint8_t* op, const uint8_t* rp) {
+    if (build_syn_pattern(k, m, op, rp, G.data(), &pl.syn[p])) return true;
+    std::memset(&pl.syn[p], 0, sizeof pl.syn[p]);
+    return false;
+  };
+  const bool fast_geo = transform_restores(k, m, S, mode, m);
+  pl.cls.resize(npat);
+  for (size_t p = 0; p < npat; ++p) {
+    const uint8_t *op = opres + p * k, *rp = rpres + p * m;
+    const size_t no = count_flags(op, k), nr = count_flags(rp, m);
+    if (no + nr < k) {
+      pl = DecodePlan{};
+      pl.status = AG_RS_ERR_NOT_ENOUGH_SHARDS;
+      return pl;
+    }
+    DecodeClass c;
+    if (no == k) {
+      c = kNone;
+    } else if (fast_geo && nr == m) {
+      c = kTransform;
+    } else if (lr_geo && (pl.lr_chunk[p] = full_chunk(rp)) != 0xFF) {
+      c = kLowRateChunk;
+    } else if (pl.syn_chunk && syn_fits(p, op, rp)) {
+      c = kSyndrome;
+    } else if (corr_geo && corr_fits(k, no, nr)) {
+      c = kCorrection;
+    } else if (x_geo && (hr == 1 || no + count_flags(rp, pl.xm_rec) >= k)) {
+      c = kWindow64;
+    } else if (x128_geo && (any_k || no + nr == k)) {
+      c = kWindow128;
+    } else {
+      c = kGeneric;
+    }
+    pl.cls[p] = c;
+    pl.used |= 1u << c;
+  }
+  return pl;
 }
 
 }  // namespace ag

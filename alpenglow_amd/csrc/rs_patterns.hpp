@@ -1,17 +1,51 @@
 // Host-only pattern bookkeeping of the decoders (no HIP calls): presence flags -> masks, the
 // per-pattern tables of the syndrome (decode_syn) and correction (decode_c) decoders, and the
-// window masks of the locator decoders (decode_x / decode_h8 / decode_x16).  Split from
-// rs_api.cpp so the CPU suite can run it under AddressSanitizer / UndefinedBehaviorSanitizer
-// (tests/native/patterns_selfcheck.cpp, tests/test_sanitizers.py).
+// window masks of the locator decoders (decode_x / decode_h8 / decode_x16), and the classifier
+// that decides which decoder restores each pattern (rs_dispatch.cpp launches what it plans).
+// Kept apart from the HIP host code so the CPU suite can run it under AddressSanitizer /
+// UndefinedBehaviorSanitizer (tests/native/patterns_selfcheck.cpp, tests/test_sanitizers.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "../../include/alpenglow_rs.h"
+#include "gf16.hpp"
 #include "rs_launch.hpp"
 
 namespace ag {
+
+// Single-chunk HighRate geometries served by the bitsliced N-point transform kernel:
+// k <= N, next_pow2(m) == N, N in {32, 64}, whole 64-byte chunks.  Returns N or 0.
+// (HighRate with a single chunk implies next_pow2(k) == N and k <= m.)
+inline unsigned xform_points(size_t k, size_t m, size_t S) {
+  if (S == 0 || S % 64 || use_high_rate(k, m) != 1) return 0;
+  const size_t n = next_pow2(m);
+  return (n == 32 || n == 64) && k <= n ? static_cast<unsigned>(n) : 0;
+}
+
+// Multi-chunk HighRate encode with a small recovery chunk (encode_mc kernel): returns the
+// chunk next_pow2(m) in {1, 2, 4} when k > chunk, k <= 64, whole 64-byte chunks; else 0.
+inline unsigned mc_chunk(size_t k, size_t m, size_t S) {
+  if (S == 0 || S % 64 || use_high_rate(k, m) != 1 || k > 64) return 0;
+  const size_t c = next_pow2(m);
+  return c <= 4 && k > c ? static_cast<unsigned>(c) : 0;
+}
+
+// LowRate encode through the transform kernel, one launch per recovery chunk: returns the
+// chunk next_pow2(k) in {32, 64} when the recovery chunks fit the launcher, else 0.
+inline unsigned lowrate_chunk(size_t k, size_t m, size_t S) {
+  if (S == 0 || S % 64 || use_high_rate(k, m) != 0) return 0;
+  const size_t c = next_pow2(k);
+  const size_t chunks = (m + c - 1) / c;
+  if (c == 32 && chunks <= 4) return 32;
+  if (c == 64 && chunks <= 3) return 64;
+  return 0;
+}
+
+// A shard size rounded up to whole 64-byte chunks.
+inline size_t padded_shard(size_t S) { return (S + 63) / 64 * 64; }
 
 // Host flag arrays (0 / nonzero bytes, one per shard) -> bit masks, 8 flags per step:
 // the per-pattern bookkeeping of a 65 536-slice batch stays well under a millisecond.
@@ -69,5 +103,64 @@ void window64_masks(bool hr, size_t k, size_t m, size_t xchunk, size_t xm_rec, c
 // next_pow2(k) (LowRate).
 void window128_masks(bool hr, size_t k, size_t m, size_t c128, const uint8_t* opres, const uint8_t* rpres,
                      uint64_t q[10]);
+
+// Per-slice present words of the coder deshreds' device-pattern paths (32 data shreds, m coding
+// shreds): word 0 = data flags | coding 0..31 << 32 (and word 1 = coding 32..m-1 when m > 32).
+// Returns whether any slice keeps more than 32 shreds; *any_full_data: some slice holds every
+// data shred (its decode is skipped, so its absent coding shreds come from the re-encode).
+bool pack_present_words(const uint8_t* dpres, const uint8_t* cpres, size_t m, size_t n, uint64_t* pres,
+                        bool* any_full_data);
+
+// The decoder that restores a pattern.  The values are fixed: last_classes[] is indexed by
+// them and Python names them (rs.DECODE_CLASSES).
+enum DecodeClass : uint8_t {
+  kNone = 0,            // no original lost
+  kTransform = 1,       // full recovery set: the N-point transform inverts the encoder
+  kGeneric = 2,         // table-driven generic kernel
+  kWindow64 = 3,        // W <= 64 locator window (decode_x / decode_h8 / decode_x16)
+  kSyndrome = 4,        // encode_mc geometries, at most 4 originals lost (decode_syn)
+  kLowRateChunk = 5,    // LowRate, one fully present 32-shard recovery chunk: its transform
+  kCorrection = 6,      // 32-point full window with few lost recovery shards (decode_c)
+  kWindow128 = 8,       // W = 128 window as two 64-point passes
+  kServerWindow64 = 9,  // the per-call server's one-slice window decode
+};
+
+// One erasure pattern repeated for every block (a repair batch, a uniform loss) is one
+// pattern: uniform store masks, and the bitsliced kernels regardless of block alignment.
+bool patterns_equal(size_t k, size_t m, size_t npat, const uint8_t* opres, const uint8_t* rpres);
+
+// Whether the transform restores a pattern with nr recovery shards present (kTransform): it
+// inverts the encoder only when all N recovery points exist (m == N; with m < N the points
+// m..N-1 were never stored), and then reads no original.
+inline bool transform_restores(size_t k, size_t m, size_t S, int mode, size_t nr) {
+  const unsigned npts = xform_points(k, m, S);
+  return mode == AG_RS_DECODE_ANY_K && npts != 0 && m == npts && nr == m;
+}
+
+// What classify_patterns decides for one decode over the first S bytes of every shard.
+struct DecodePlan {
+  int status = AG_RS_OK;          // or AG_RS_ERR_NOT_ENOUGH_SHARDS: nothing else is set then
+  size_t npat = 0;                // patterns after the equal-patterns collapse
+  std::vector<uint8_t> cls;       // DecodeClass per pattern
+  std::vector<uint8_t> lr_chunk;  // kLowRateChunk patterns: the recovery chunk they restore from
+  std::vector<SynPattern> syn;    // kSyndrome patterns (all zero for the others); empty without syn_chunk
+  uint32_t used = 0;              // bit c: some pattern has class c
+  int hr = 0;                     // use_high_rate(k, m)
+  unsigned npts = 0;              // xform_points(k, m, S)
+  unsigned syn_chunk = 0;         // mc_chunk(k, m, S) where the syndrome decoder's tiling allows it
+  size_t xchunk = 0, xw = 0;      // W <= 64 window: chunk and width (0: no such window)
+  size_t xm_rec = 0;              // recovery shards inside that window
+  size_t c128 = 0;                // W = 128 window: next_pow2(m) (HighRate) or next_pow2(k) (LowRate)
+  size_t cps = 0;                 // S / 64
+  bool per_lane = false;          // per-block patterns on tiles that straddle blocks (cps % 64 != 0)
+  bool uses(DecodeClass c) const { return (used >> c) & 1u; }
+};
+
+// Classifies every pattern of a decode call (npat == 1 or npat == nblocks; mode AG_RS_DECODE_*):
+// one pass over the flags, no allocation per pattern.  Each pattern takes the first class of
+// none, transform, lowrate_chunk, syndrome, correction, window64, window128, generic that
+// admits it.
+DecodePlan classify_patterns(size_t k, size_t m, size_t S, size_t nblocks, size_t npat, int mode,
+                             const uint8_t* opres, const uint8_t* rpres);
 
 }  // namespace ag

@@ -90,7 +90,7 @@ hipError_t launch_pipe_merge_lens(const uint32_t* fresh, const uint64_t* present
 
 // The ReedSolomonCoder::deshred patterns of the kept shreds on the device (32:32 HighRate,
 // window W = 64: recovery j at position j, original i at 32 + i), for the per-lane decode_x
-// kernel (the patterns rs_api.cpp's decode_device builds on the host for ANY_K):
+// kernel (the patterns rs_dispatch.cpp's run_window64 builds on the host for ANY_K):
 //   xm[s] = erased positions (locator), xm[n + 2 s] = survivors loaded (the present originals,
 //   then recovery shards in index order up to 32), xm[n + 2 s + 1] = originals restored.
 // Slices with fewer than 32 kept shreds, or nothing to restore, get empty masks (no loads, no
@@ -103,7 +103,7 @@ hipError_t launch_pipe_patterns(const uint64_t* present, uint64_t nslices, uint6
 // The same for CodingOnly slices (LowRate 32:64) in the W = 128 window of the two-pass decoder:
 // present[2 s] = data bits | coding 0..31 << 32, present[2 s + 1] = coding 32..63; xm =
 // decode_rows128's m6 [n][6], then the pass-1 and pass-2 (survivors, restored) pairs [n][2]
-// each (rs_api.cpp's class-8 layout).
+// each (rs_dispatch.cpp's run_window128 layout, DecodeClass kWindow128).
 hipError_t launch_pipe_patterns128(const uint64_t* present, uint64_t nslices, uint64_t* xm, uint8_t* few,
                                    hipStream_t stream);
 // mask[s] = ~0 (store every coding shard of the re-encode) when the slice decoded and its

@@ -1,7 +1,8 @@
 // Host side of the composed shredders: ag_shredder_shred_batch[_var|_kind] and
 // ag_shredder_deshred_batch[_kind] (include/alpenglow_rs.h), the four shredders of shredder.rs
 // (Regular, CodingOnly, PETS, AONT) chained on the device from the batched stages of rs_api.cpp
-// (slice framing, ReedSolomonCoder, Merkle trees, signatures, all-or-nothing transforms) and
+// (slice framing, ReedSolomonCoder, Merkle trees, signatures, all-or-nothing transforms; the
+// coder's encode / decode dispatch is rs_dispatch.cpp) and
 // the glue kernels of shredder.hip / wire.hip.
 //
 // The entry points keep what is their own (argument checks, framing, the coder call, how a

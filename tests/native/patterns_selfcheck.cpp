@@ -9,11 +9,17 @@
 //     with lost recovery shards (K read back from the kernel's table picks);
 //   * window64_masks / window128_masks: exactly k survivors under ANY_K, no erased position
 //     loaded, every restored position erased;
-//   * pack_flags / count_flags against a byte loop.
+//   * pack_flags / count_flags against a byte loop;
+//   * classify_patterns: a table of geometries and patterns with the decoder class each must
+//     take, and the rules every class obeys over random patterns.
 // Prints "ok" and exits 0, or names the first failing check and exits 1.
 #include <cstdio>
+#include <algorithm>
 #include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <random>
+#include <utility>
 #include <vector>
 
 #include "gf16.hpp"
@@ -223,6 +229,198 @@ static void check_flags(std::mt19937_64& rng) {
   }
 }
 
+// n flags, all present but the [from, to) ranges
+static std::vector<uint8_t> flags(size_t n, std::initializer_list<std::pair<size_t, size_t>> lost) {
+  std::vector<uint8_t> f(n, 1);
+  for (const auto& r : lost)
+    for (size_t i = r.first; i < r.second; ++i) f[i] = 0;
+  return f;
+}
+
+struct ClassCase {
+  size_t k, m, S, nblocks;
+  int mode;
+  std::vector<std::vector<uint8_t>> op, rp;  // one entry per pattern
+  int status;
+  std::vector<uint8_t> cls;  // expected class per pattern (after the collapse)
+  int lr_chunk;              // of the kLowRateChunk patterns; -1: none expected
+};
+
+static void check_classify_table() {
+  const int A = AG_RS_DECODE_ANY_K, E = AG_RS_DECODE_EXACT;
+  const auto lose16 = flags(32, {{0, 16}}), all32 = flags(32, {});
+  // mixed per-block patterns of the 32:32 code: nothing lost / full recovery set / 4 recovery
+  // shards lost / 17 recovery shards lost
+  const std::vector<std::vector<uint8_t>> mix_o = {all32, lose16, lose16, flags(32, {{0, 8}})};
+  const std::vector<std::vector<uint8_t>> mix_r = {flags(32, {{0, 5}}), all32, flags(32, {{0, 4}}),
+                                                   flags(32, {{4, 21}})};
+  // 32:64: nothing lost / recovery chunk 0 whole / chunk 1 whole / enough inside the W = 64
+  // sub-window / only both chunks together
+  const std::vector<std::vector<uint8_t>> lr_o = {all32, flags(32, {{0, 32}}), flags(32, {{0, 32}}),
+                                                  flags(32, {{0, 8}}), lose16};
+  const std::vector<std::vector<uint8_t>> lr_r = {flags(64, {{0, 3}}), flags(64, {{40, 64}}), flags(64, {{0, 32}}),
+                                                  flags(64, {{0, 3}, {40, 44}}), flags(64, {{0, 24}, {40, 44}})};
+  const std::vector<ClassCase> cases = {
+      {32, 32, 4096, 1, A, {lose16}, {all32}, AG_RS_OK, {kTransform}, -1},
+      {32, 32, 4096, 1, E, {lose16}, {all32}, AG_RS_OK, {kWindow64}, -1},
+      // the correction decoder from 64 * 256 columns on (64 columns per block here)
+      {32, 32, 4096, 256, A, {lose16}, {flags(32, {{0, 4}})}, AG_RS_OK, {kCorrection}, -1},
+      {32, 32, 4096, 255, A, {lose16}, {flags(32, {{0, 4}})}, AG_RS_OK, {kWindow64}, -1},
+      {16, 4, 4096, 1, A, {flags(16, {{0, 2}})}, {flags(4, {})}, AG_RS_OK, {kSyndrome}, -1},
+      {16, 4, 4096, 1, E, {flags(16, {{0, 2}})}, {flags(4, {})}, AG_RS_OK, {kWindow64}, -1},
+      {32, 64, 1024, 1, A, {flags(32, {{0, 32}})}, {flags(64, {{0, 32}})}, AG_RS_OK, {kLowRateChunk}, 1},
+      {64, 64, 4096, 1, A, {flags(64, {{0, 16}})}, {flags(64, {{0, 8}})}, AG_RS_OK, {kWindow128}, -1},
+      {100, 100, 1024, 1, A, {flags(100, {{0, 10}})}, {flags(100, {{0, 5}})}, AG_RS_OK, {kGeneric}, -1},
+      {100, 100, 1024, 1, E, {flags(100, {{0, 10}})}, {flags(100, {{0, 5}})}, AG_RS_OK, {kGeneric}, -1},
+      // no original lost: none, whatever the geometry
+      {32, 32, 4096, 1, A, {all32}, {flags(32, {{0, 9}})}, AG_RS_OK, {kNone}, -1},
+      {100, 100, 1024, 1, E, {flags(100, {})}, {flags(100, {{0, 50}})}, AG_RS_OK, {kNone}, -1},
+      // fewer than k shards present
+      {32, 32, 4096, 1, A, {lose16}, {flags(32, {{0, 17}})}, AG_RS_ERR_NOT_ENOUGH_SHARDS, {}, -1},
+      {16, 4, 4096, 1, A, {flags(16, {{0, 3}})}, {flags(4, {{0, 2}})}, AG_RS_ERR_NOT_ENOUGH_SHARDS, {}, -1},
+      // per-block patterns, mixed classes in one call: 64 tiles per block, then per-lane tiles
+      {32, 32, 4096 * 64, 4, A, mix_o, mix_r, AG_RS_OK, {kNone, kTransform, kCorrection, kWindow64}, -1},
+      {32, 32, 4096 * 64, 4, E, mix_o, mix_r, AG_RS_OK, {kNone, kWindow64, kWindow64, kWindow64}, -1},
+      {32, 32, 192, 4, A, mix_o, mix_r, AG_RS_OK, {kNone, kTransform, kWindow64, kWindow64}, -1},
+      {64, 64, 4096, 3, A, {flags(64, {}), flags(64, {{0, 16}}), flags(64, {{0, 16}})},
+       {flags(64, {{0, 3}}), flags(64, {}), flags(64, {{0, 8}})}, AG_RS_OK, {kNone, kTransform, kWindow128}, -1},
+      {64, 64, 4096, 3, E, {flags(64, {}), flags(64, {{0, 16}}), flags(64, {{0, 16}})},
+       {flags(64, {{0, 3}}), flags(64, {}), flags(64, {{0, 8}})}, AG_RS_OK, {kNone, kGeneric, kGeneric}, -1},
+      {32, 64, 4096, 5, E, lr_o, lr_r, AG_RS_OK, {kNone, kGeneric, kWindow128, kGeneric, kGeneric}, -1},
+      // equal patterns collapse to one
+      {32, 32, 4096, 3, A, {lose16, lose16, lose16}, {all32, all32, all32}, AG_RS_OK, {kTransform}, -1},
+  };
+  for (size_t ci = 0; ci < cases.size(); ++ci) {
+    const ClassCase& t = cases[ci];
+    std::vector<uint8_t> op, rp;
+    for (const auto& v : t.op) op.insert(op.end(), v.begin(), v.end());
+    for (const auto& v : t.rp) rp.insert(rp.end(), v.begin(), v.end());
+    const DecodePlan pl = classify_patterns(t.k, t.m, t.S, t.nblocks, t.op.size(), t.mode, op.data(), rp.data());
+    CHECK(pl.status == t.status, "classify case %zu: status %d, expected %d", ci, pl.status, t.status);
+    if (t.status) continue;
+    CHECK(pl.npat == t.cls.size() && pl.cls == t.cls, "classify case %zu (%zu:%zu): class %d...", ci, t.k, t.m,
+          pl.cls.empty() ? -1 : pl.cls[0]);
+    uint32_t used = 0;
+    for (size_t p = 0; p < pl.npat; ++p) {
+      used |= 1u << pl.cls[p];
+      if (pl.cls[p] == kLowRateChunk) CHECK(pl.lr_chunk[p] == t.lr_chunk, "classify case %zu: chunk %d", ci, pl.lr_chunk[p]);
+    }
+    CHECK(pl.used == used, "classify case %zu: used %x", ci, pl.used);
+  }
+  // the 32:64 row above under ANY_K, with both chunk choices in one call
+  std::vector<uint8_t> op, rp;
+  for (const auto& v : lr_o) op.insert(op.end(), v.begin(), v.end());
+  for (const auto& v : lr_r) rp.insert(rp.end(), v.begin(), v.end());
+  const DecodePlan pl = classify_patterns(32, 64, 4096, 5, 5, A, op.data(), rp.data());
+  const std::vector<uint8_t> want = {kNone, kLowRateChunk, kLowRateChunk, kWindow64, kWindow128};
+  CHECK(pl.status == AG_RS_OK && pl.cls == want, "classify 32:64 per block");
+  CHECK(pl.lr_chunk[1] == 0 && pl.lr_chunk[2] == 1, "classify 32:64 chunks %d %d", pl.lr_chunk[1], pl.lr_chunk[2]);
+  CHECK(pl.hr == 0 && pl.xchunk == 32 && pl.xw == 64 && pl.xm_rec == 32 && pl.c128 == 32 && pl.cps == 64 && !pl.per_lane,
+        "classify 32:64 geometry");
+}
+
+// The rules of the classes over random patterns: what a class may be given, read off the
+// decoders' own requirements, not off the classifier.
+static void check_classify_random(std::mt19937_64& rng) {
+  const size_t geos[][2] = {{32, 32}, {32, 64}, {32, 33}, {16, 4}, {64, 64}, {40, 64}, {20, 80}};
+  for (const auto& g : geos) {
+    const size_t k = g[0], m = g[1];
+    std::vector<uint16_t> G;
+    if (use_high_rate(k, m) == 1) {
+      G.resize(m * k);
+      hr_generator(k, m, G.data());
+    }
+    for (int it = 0; it < 40; ++it) {
+      // 64 tiles per block with the column threshold of the correction class met (it % 4 ==
+      // 0) or not, per-lane tiles, one pattern
+      const size_t S = it % 4 == 2 ? 192 : 4096, nblocks = it % 4 == 0 ? 256 : 16;
+      const size_t npat = it % 4 == 3 ? 1 : nblocks;
+      const int mode = it & 4 ? AG_RS_DECODE_EXACT : AG_RS_DECODE_ANY_K;
+      const unsigned lo = rng() % 5, lr = rng() % 5;
+      std::vector<uint8_t> op(npat * k), rp(npat * m);
+      for (size_t p = 0; p < npat; ++p) {
+        // a valid pattern: redrawn until k shards are present; some with nothing lost, some
+        // with the full recovery set, some with one whole 32-shard recovery chunk
+        do {
+          for (size_t i = 0; i < k; ++i) op[p * k + i] = rng() % 8 >= lo ? static_cast<uint8_t>(1 + rng() % 255) : 0;
+          for (size_t i = 0; i < m; ++i) rp[p * m + i] = rng() % 8 >= lr;
+          const unsigned pick = rng() % 8;
+          if (pick == 0) std::fill_n(&op[p * k], k, 1);
+          if (pick == 1) std::fill_n(&rp[p * m], m, 1);
+          if (pick == 2 && m >= 64) std::fill_n(&rp[p * m + 32 * (rng() % 2)], 32, 1);
+        } while (count_flags(&op[p * k], k) + count_flags(&rp[p * m], m) < k);
+      }
+      const DecodePlan pl = classify_patterns(k, m, S, nblocks, npat, mode, op.data(), rp.data());
+      CHECK(pl.status == AG_RS_OK && pl.npat == npat && pl.cls.size() == npat, "classify %zu:%zu: plan shape", k, m);
+      const unsigned npts = xform_points(k, m, S);
+      uint32_t used = 0;
+      for (size_t p = 0; p < npat; ++p) {
+        const uint8_t *o = &op[p * k], *r = &rp[p * m];
+        const size_t no = count_flags(o, k), nr = count_flags(r, m);
+        const uint8_t c = pl.cls[p];
+        used |= 1u << c;
+        // exactly one class, and a named one
+        CHECK(c == kNone || c == kTransform || c == kGeneric || c == kWindow64 || c == kSyndrome ||
+                  c == kLowRateChunk || c == kCorrection || c == kWindow128,
+              "classify %zu:%zu: class %d", k, m, c);
+        CHECK((c == kNone) == (no == k), "classify %zu:%zu: none iff no original lost", k, m);
+        if (c == kTransform)
+          CHECK(mode == AG_RS_DECODE_ANY_K && nr == m && npts != 0 && m == npts, "classify %zu:%zu: transform", k, m);
+        if (c == kSyndrome) {
+          SynPattern sp;
+          CHECK(!G.empty() && build_syn_pattern(k, m, o, r, G.data(), &sp), "classify %zu:%zu: syndrome", k, m);
+          CHECK(std::memcmp(&sp, &pl.syn[p], sizeof sp) == 0, "classify %zu:%zu: syndrome pattern", k, m);
+        }
+        if (c == kCorrection)
+          CHECK(corr_fits(k, no, nr) && nblocks * (S / 64) >= 64 * 256, "classify %zu:%zu: correction", k, m);
+        if (c == kLowRateChunk) {
+          const size_t j = pl.lr_chunk[p];
+          CHECK(32 * (j + 1) <= m && count_flags(r + 32 * j, 32) == 32, "classify %zu:%zu: chunk %zu not whole", k, m, j);
+        }
+        // the class of a pattern does not depend on the other patterns of the call
+        if (npat > 1 && p % 16 == 0) {
+          std::vector<uint8_t> o2(o, o + k), r2(r, r + m);
+          for (size_t q = 1; q < npat; ++q) {  // the same call with every other pattern replaced
+            o2.insert(o2.end(), k, 1);
+            r2.insert(r2.end(), m, q & 1);
+          }
+          o2[k] = 0;  // (and never equal patterns: pattern 1 loses original 0 alone)
+          r2[m] = 1;
+          const DecodePlan alone = classify_patterns(k, m, S, nblocks, npat, mode, o2.data(), r2.data());
+          CHECK(alone.status == AG_RS_OK && alone.npat == npat && alone.cls[0] == c,
+                "classify %zu:%zu: class %d of a pattern became %d among other patterns", k, m, c, alone.cls[0]);
+        }
+      }
+      CHECK(pl.used == used, "classify %zu:%zu: used", k, m);
+    }
+  }
+}
+
+static void check_present_words(std::mt19937_64& rng) {
+  for (size_t m : {size_t{32}, size_t{33}, size_t{64}}) {
+    const size_t n = 37, wps = m == 32 ? 1 : 2;
+    std::vector<uint8_t> d(n * 32), c(n * m);
+    for (auto& v : d) v = (rng() & 3) ? static_cast<uint8_t>(rng() | 1) : 0;
+    for (auto& v : c) v = (rng() & 1) ? static_cast<uint8_t>(rng() | 1) : 0;
+    std::fill_n(&d[5 * 32], 32, 1);
+    std::vector<uint64_t> w(n * wps);
+    bool full = false, surplus = false;
+    const bool got = pack_present_words(d.data(), c.data(), m, n, w.data(), &full);
+    for (size_t b = 0; b < n; ++b) {
+      const uint64_t w0 = pack_flags(&d[b * 32], 32) | (pack_flags(&c[b * m], 32) << 32);
+      CHECK(w[wps * b] == w0, "pack_present_words word 0 (m=%zu)", m);
+      if (wps == 2) CHECK(w[2 * b + 1] == pack_flags(&c[b * m + 32], m - 32), "pack_present_words word 1 (m=%zu)", m);
+      surplus |= count_flags(&d[b * 32], 32) + count_flags(&c[b * m], m) > 32;
+    }
+    CHECK(got == surplus && full, "pack_present_words flags (m=%zu)", m);
+  }
+}
+
+static void check_classify(std::mt19937_64& rng) {
+  check_classify_table();
+  check_classify_random(rng);
+}
+
 int main() {
   std::mt19937_64 rng(0xA19E);
   check_flags(rng);
@@ -231,6 +429,8 @@ int main() {
   check_syn(rng);
   check_corr(rng);
   check_windows(rng);
+  check_classify(rng);
+  check_present_words(rng);
   if (g_fail) return 1;
   std::printf("ok\n");
   return 0;

@@ -62,7 +62,7 @@ def gpu_decode(ctx, dev, orig: np.ndarray, rec: np.ndarray, opres, rpres, mode):
 
 
 # decode_c serves batches of at least this many 64-byte shard columns (256 tiles: fewer tiles
-# than CUs are latency-bound and take the window decoder) -- rs_api.cpp decode_cols corr_geo
+# than CUs are latency-bound and take the window decoder) -- rs_patterns.cpp classify_patterns corr_geo
 CORR_MIN_COLS = 64 * 256
 
 
@@ -1105,6 +1105,59 @@ def test_decode_device_patterns_lost_coding(ctx, dev, S, n):
     assert np.array_equal(got, blocks)
     parts = 1  # one decode, the tail (if any) as its last column
     assert rs.last_decode_classes(ctx) == {"window64": parts * restore, "none": parts * (n - restore)}
+
+
+def test_pattern_caches_across_classes(ctx, dev):
+    """The pattern uploads that launchers share, on one context, every call against the oracle
+    encode.  (a) One store-mask cache serves the LowRate chunk transform, the 32-point transform
+    and its tail variant: a 32:64 decode from recovery chunk 1, a 32:32 decode with the equal
+    mask word, a 32:32 decode of shards with a 16-byte tail, and the first call again.  (b) The
+    device-pattern route overwrites the window decoder's masks and constants: the one-pattern
+    window decode before it must rebuild them when it runs again unchanged."""
+    k = 32
+
+    def case(seed, m, S, n):
+        blocks = _blocks(seed, n, k, S)
+        return blocks, ro_c.encode_blocks(blocks, m, threads=8)
+
+    def decode(case, lost, lost_r, classes):
+        blocks, rec = case
+        m = rec.shape[1]
+        d_o, d_r = blocks.copy(), rec.copy()
+        d_o[:, lost] = 0x5A
+        d_r[:, lost_r] = 0xA5
+        op = [0 if i in lost else 1 for i in range(k)]
+        rp = [0 if j in lost_r else 1 for j in range(m)]
+        assert np.array_equal(gpu_decode(ctx, dev, d_o, d_r, op, rp, rs.DECODE_ANY_K), blocks), (m, lost, lost_r)
+        assert rs.last_decode_classes(ctx) == classes
+
+    # (a)
+    low, mid, tail = case(5100, 64, 64, 3), case(5101, 32, 64, 3), case(5102, 32, 80, 3)
+    decode(low, list(range(16)), list(range(32)), {"lowrate_chunk": 1})
+    decode(mid, list(range(16)), [], {"transform": 1})
+    decode(tail, [3, 17, 30], [], {"transform": 1})
+    decode(low, list(range(16)), list(range(32)), {"lowrate_chunk": 1})
+
+    # (b)
+    one = case(5103, 32, 192, 5)
+    lost, lost_r = [1, 4, 9, 12, 20, 21, 27, 31], list(range(3, 20))
+    decode(one, lost, lost_r, {"window64": 1})
+    n, S, m = 131, 192, 32
+    rng = random.Random(5104)
+    blocks, rec = case(5104, m, S, n)
+    d_o, d_r, op, rp = blocks.copy(), rec.copy(), [], []
+    restore = 0
+    for b in range(n):
+        lost_c = set(rng.sample(range(m), rng.randint(1, 12)))
+        erased = set() if b % 11 == 3 else set(rng.sample(range(k), rng.randint(8, 20)))
+        restore += 1 if erased else 0
+        op += [0 if i in erased else 1 for i in range(k)]
+        rp += [0 if j in lost_c else 1 for j in range(m)]
+        d_o[b, list(erased)] = 0x77
+        d_r[b, list(lost_c)] = 0x99
+    assert np.array_equal(gpu_decode(ctx, dev, d_o, d_r, op, rp, rs.DECODE_ANY_K), blocks)
+    assert rs.last_decode_classes(ctx) == {"window64": restore, "none": n - restore}
+    decode(one, lost, lost_r, {"window64": 1})
 
 
 @pytest.mark.parametrize("k,m,n", [(32, 32, 25), (32, 32, 64), (32, 64, 11), (20, 40, 9)])
