@@ -28,14 +28,18 @@ ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 CXX = os.environ.get("CXX_HOST", "g++")
 
-SOURCES = ["rs_kernels.hip", "rs_xform64.hip", "rs_decode_c.hip", "rs_var.hip", "merkle.hip", "cipher.hip", "ed25519.hip", "wire.hip", "slice.hip", "shredder.hip", "rs_api.cpp", "rs_dispatch.cpp", "shredder_api.cpp", "rs_patterns.cpp", "gf16.cpp"]
-HEADERS = ["gf16.hpp", "rs_device.hpp", "rs_xform.hpp", "rs_launch.hpp", "rs_consts.inc", "rs_patterns.hpp", "rs_ctx.hpp", "merkle.hpp", "sha256.hpp", "cipher.hpp", "ed25519.hpp", "ed25519_core.hpp", "wire.hpp", "slice.hpp", "shredder.hpp", "unaligned.hpp"]
+# one TU per RS kernel family (the slowest to compile first: they set the build's wall time)
+RS_KERNEL_SOURCES = ["rs_tile64.hip", "rs_window.hip", "rs_generic.hip", "rs_coder_kernels.hip"]
+SOURCES = [*RS_KERNEL_SOURCES, "rs_xform64.hip", "rs_decode_c.hip", "rs_var.hip", "merkle.hip", "cipher.hip", "ed25519.hip", "wire.hip", "slice.hip", "shredder.hip", "rs_api.cpp", "rs_dispatch.cpp", "shredder_api.cpp", "rs_patterns.cpp", "gf16.cpp"]
+HEADERS = ["gf16.hpp", "rs_device.hpp", "rs_xform.hpp", "rs_xform8.hpp", "rs_decode_pk.hpp", "rs_launch.hpp", "rs_consts.inc", "rs_patterns.hpp", "rs_ctx.hpp", "merkle.hpp", "sha256.hpp", "cipher.hpp", "ed25519.hpp", "ed25519_core.hpp", "wire.hpp", "slice.hpp", "shredder.hpp", "unaligned.hpp"]
 # -fno-slp-vectorize: the SLP vectoriser packs the bitsliced XOR networks into <2 x i32>
 # ops, which lengthens live ranges (measured +40 VGPRs on the transform kernel).
 # -amdgpu-promote-alloca-to-vector-limit: keeps the four-Russians tables of decode_x and
 # decode_syn (4 x 16 words, wave-uniform picks) in VGPRs (v_movrels) instead of scratch.
-# rs_kernels.hip and rs_decode_c.hip need 2048 (at 512 two of decode_syn's four tables land in scratch; no
-# other RS kernel's VGPR or scratch use changes, checked with
+# The RS kernel family TUs (RS_KERNEL_SOURCES, once one file), rs_xform64.hip and rs_decode_c.hip
+# get 2048: rs_tile64.hip needs it (at 512 two of decode_syn's four tables land in scratch) and
+# the other families keep the setting they were built and measured with as one TU (no other RS
+# kernel's VGPR or scratch use differs between the two, checked with
 # -Rpass-analysis=kernel-resource-usage); the other sources keep 512, the setting their
 # kernels were measured with (2048 would change the Ed25519 kernels' scratch use).
 HIP_FLAGS = [*os.environ.get("AG_RS_EXTRA_HIPFLAGS", "").split(),
@@ -101,7 +105,7 @@ def build(force: bool = False) -> str:
         obj = os.path.join(OBJDIR, s + ".o")
         objs.append(obj)
         deps = [os.path.join(CSRC, h) for h in _deps(s)] + [os.path.join(INCLUDE, "alpenglow_rs.h")]
-        limit = 2048 if s in ("rs_kernels.hip", "rs_xform64.hip", "rs_decode_c.hip") else 512
+        limit = 2048 if s in (*RS_KERNEL_SOURCES, "rs_xform64.hip", "rs_decode_c.hip") else 512
         cmd = [HIPCC, *HIP_FLAGS, "-mllvm", f"-amdgpu-promote-alloca-to-vector-limit={limit}", "-c", src, "-o", obj]
         # the stamp holds the full compile command: a flag change (AG_RS_EXTRA_HIPFLAGS
         # diagnostics, the promote-alloca limit) rebuilds the object even when no file changed
@@ -116,7 +120,7 @@ def build(force: bool = False) -> str:
         _run(cmd)
         with open(stamp, "w") as f:
             f.write(" ".join(cmd))
-    with cf.ThreadPoolExecutor(max_workers=len(SOURCES)) as ex:
+    with cf.ThreadPoolExecutor(max_workers=max(1, min(len(jobs), int(os.environ.get("MAX_JOBS", 16))))) as ex:
         list(ex.map(_compile, jobs))
     if force or jobs or _mtime(LIB) < max(_mtime(o) for o in objs):
         tmp = LIB + ".tmp"

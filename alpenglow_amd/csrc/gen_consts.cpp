@@ -325,7 +325,7 @@ int main(int argc, char** argv) {
   // Basis change between the crate's Cantor-basis coordinates and the polynomial basis of
   // GF(2)[a] / 0x1002D: L(x) = a^log[x] (the LFSR state the crate's exp table inverts).
   // In the polynomial basis a multiply by `a` is a shift plus 3 XORs (a^16 = a^5 + a^3 + a^2 +
-  // 1), so a runtime constant multiply is a 16-step Horner scheme (rs_kernels.hip mul_rt_poly).
+  // 1), so a runtime constant multiply is a 16-step Horner scheme (rs_device.hpp mul_rt_poly).
   // Matrix 0 = L (Cantor -> poly), 1 = L^-1; emitted as CSE programs like the skew constants.
   {
     std::vector<uint16_t> st(ag::kGfModulus);

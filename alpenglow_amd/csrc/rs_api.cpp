@@ -1,6 +1,6 @@
 // Host side of libalpenglow_rs.so: the C ABI declared in include/alpenglow_rs.h.
 //
-// Mirrors three reference interfaces on top of the HIP kernels (rs_kernels.hip):
+// Mirrors three reference interfaces on top of the HIP kernels (the rs_*.hip TUs, rs_launch.hpp):
 //   * the reed-solomon-simd 3.1.0 encoder/decoder API the reference wrapper calls
 //     (reed_solomon.rs:9,64-66,96-125,150-180,214-226)
 //   * ReedSolomonCoder (reed_solomon.rs:47-232) and the ValidatedShreds checks

@@ -553,7 +553,7 @@ int run_window64(const DecodeCall& d, const DecodePlan& pl) {
                    &xm[npat + 2 * p], &xm[npat + 2 * p + 1]);
   }
   // polynomial-basis constants (one word per position) for decode_x16 (W = 64) and for
-  // per-lane patterns; bitsliced matrices for decode_x<4>'s wave-uniform four-Russians products
+  // per-lane patterns; bitsliced matrices for decode_x's wave-uniform four-Russians products
   const bool poly = xw == 64 || pl.per_lane;
   if (!c->xmask.holds(xm) || xw != c->xmask_w || poly != c->xmask_poly) {
     if ((st = c->xmask.renew(xm.size() * 8, c->stream)) ||

@@ -1,4 +1,6 @@
-// Kernel parameter blocks and launchers (host side of rs_kernels.hip).
+// Kernel parameter blocks and launchers (host side of the RS kernel TUs: rs_tile64.hip,
+// rs_window.hip, rs_xform64.hip, rs_var.hip, rs_decode_c.hip, rs_generic.hip,
+// rs_coder_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +26,7 @@ struct XformParams {
   uint32_t chunks_per_shard;   // shard_bytes / 64
   uint64_t total_columns;         // nblocks * chunks_per_shard
   uint32_t out_low_half;          // decode: every stored shard is < N / 2 (pruned FFT)
-  uint32_t skip_idle;             // xform<4> with per-block masks: tiles whose blocks all have
+  uint32_t skip_idle;             // xform_kernel with per-block masks: tiles whose blocks all have
                                   // mask 0 exit before loading (re-encodes of a few slices)
   uint32_t tail_bytes;            // T = S mod 64 (even), TAIL kernels: chunk chunks_per_shard - 1 of
                                   // every shard is the crate's split tail (T/2 low bytes, then T/2
@@ -36,7 +38,7 @@ enum class XformKind { kEncode32, kDecode32, kEncode64, kDecode64 };
 // Encode kernels, as bits of the per-context record of the last encode call (test aid:
 // ag_rs_internal_last_encode_kernels).
 enum EncodeKernelBit : uint32_t {
-  kEkXform4 = 1u << 0,    // xform_kernel<4, 32, 0>: the headline 32-point encode
+  kEkXform4 = 1u << 0,    // xform_kernel<32, 0>: the headline 32-point encode
   kEkXform8 = 1u << 1,    // xform8_kernel<32, 0>: small batches, 8 / 16 KiB shards
   kEkXformH8 = 1u << 2,   // xform_h8: 64-point encode
   kEkEncodeMc = 1u << 3,  // encode_mc: multi-chunk HighRate (16:4)
@@ -47,7 +49,7 @@ enum EncodeKernelBit : uint32_t {
   kEkVar = 1u << 8,       // var_encode_kernel: mixed shred sizes over the column table (rs_var.hip)
 };
 // The 32-point encode kernel launch_xform(kEncode32, p) runs: xform8 for batches of fewer
-// than 256 tiles and for 8 / 16 KiB shards (chunks_per_shard 128 / 256), else xform<4>.
+// than 256 tiles and for 8 / 16 KiB shards (chunks_per_shard 128 / 256), else xform_kernel.
 inline EncodeKernelBit encode32_kernel(const XformParams& p) {
   const uint64_t groups = (p.total_columns + 63) / 64;
   return groups < 256 || p.chunks_per_shard == 128 || p.chunks_per_shard == 256 ? kEkXform8 : kEkXform4;
@@ -192,6 +194,11 @@ struct DecodeXParams {
 enum DecodeXKernelBit : uint32_t { kDxPkFused = 1, kDxPk = 2, kDxH8Fused = 4, kDxH8 = 8, kDxX16 = 16, kDxVar = 32 };
 hipError_t launch_decode_x(unsigned W, int pass, const DecodeXParams& p, uint64_t ntiles, hipStream_t stream,
                            uint32_t* which = nullptr);
+// launch_decode_x's kernels on 64-column tiles (rs_tile64.hip): decode_x (W = 32) and decode_x16
+// (W = 64: pass 0; W = 128: pass 1 / 2 with the loaded and output halves din / dout)
+hipError_t launch_decode_x32(bool per_lane, dim3 grid, const DecodeXParams& p, hipStream_t stream);
+hipError_t launch_decode_x16(int pass, unsigned din, unsigned dout, dim3 grid, const DecodeXParams& p,
+                             hipStream_t stream);
 hipError_t launch_decode_rows128(const uint64_t* m6, uint32_t npat, const GfDeviceTables& t, uint32_t* rows,
                                  hipStream_t stream);
 // rows for npat patterns: emask[p] = erased positions (locator), pmask as above.

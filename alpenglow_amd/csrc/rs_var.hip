@@ -10,7 +10,7 @@
 //
 // Kernels
 //   var_pad_kernel     coder_pad_kernel with the data region 32 * S_b of each slice
-//   var_encode_kernel  xform_kernel<4, 32, 0>'s 32-point HighRate encode; lane = one whole
+//   var_encode_kernel  xform_kernel<32, 0>'s 32-point HighRate encode; lane = one whole
 //                      column; optional per-slice store masks (the deshred's re-encode)
 //   var_decode_kernel  decode_h8_kernel<-1, 0, 0, 0>'s W = 64 per-lane window decode with the
 //                      fused coding restore
@@ -106,10 +106,10 @@ __device__ __forceinline__ void shr_bytes_pl(const uint32_t* in, uint32_t j, uin
     out[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], b);
   });
 }
-// keep the low `len` bytes of the NW-word value v (len per lane)
-template <int NW>
+// keep the low `len` bytes of the WORDS-word value v (len per lane)
+template <int WORDS>
 __device__ __forceinline__ void keep_bytes_pl(uint32_t* v, uint32_t len) {
-  static_for<NW>([&](auto K) {
+  static_for<WORDS>([&](auto K) {
     constexpr int k = decltype(K)::value;
     const int keep = static_cast<int>(len) - 4 * k;
     const uint32_t m = keep >= 4 ? ~0u : keep <= 0 ? 0u : (1u << (8 * keep)) - 1;
@@ -229,7 +229,7 @@ __device__ __forceinline__ void var_store_planes(uint8_t* dst, uint32_t T, const
 
 // ---- padding writer and strip ----------------------------------------------------------
 
-// coder_pad_kernel (rs_kernels.hip) with the data region 32 * sizes[b] of each slice: with a
+// coder_pad_kernel (rs_coder_kernels.hip) with the data region 32 * sizes[b] of each slice: with a
 // payload source one workgroup copies one slice (the piece holding byte `len` merged with 0x80
 // 00..); in place only the pieces from that one on are written, one wave per slice.
 __global__ __launch_bounds__(256) void var_pad_kernel(const uint8_t* __restrict__ payload, uint64_t payload_stride,
@@ -295,13 +295,12 @@ __global__ __launch_bounds__(256) void var_strip_kernel(const uint8_t* __restric
 
 // ---- 32-point HighRate encode over the column table ------------------------------------
 
-// xform_kernel<4, 32, 0> (rs_kernels.hip) with lane = one whole column of the batch: 4 waves x
+// xform_kernel<32, 0> (rs_tile64.hip) with lane = one whole column of the batch: 4 waves x
 // 64 lanes, wave w owns data shards 8 w + t in passes A and C.  out_mask (optional): one word
 // per slice, bit s set => coding shard s is stored; a tile whose slices store nothing exits
 // before loading.
 __global__ __launch_bounds__(256, 2) void var_encode_kernel(const VarParams p) {
-  constexpr int NW = 4;
-  __shared__ uint4 lds[4 * NW * 4 * kXfLanes];
+  __shared__ uint4 lds[16 * 4 * kXfLanes];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t tile = dev::xcd_tile(blockIdx.x, gridDim.x);
@@ -318,14 +317,14 @@ __global__ __launch_bounds__(256, 2) void var_encode_kernel(const VarParams p) {
     if (g.ok) var_load_planes(in + static_cast<uint64_t>(s) * g.S, g.T, ra[t]);
     else static_for<16>([&](auto P) { ra[t][decltype(P)::value] = 0u; });
   });
-  xf_pass_a<NW, 32>(wave, ra);
+  xf_pass_a<32>(wave, ra);
   Regs8 rb;
-  xf_exchange_ab<NW>(wave, lane, lds, ra, rb);
-  xf_pass_b<NW, 32, 0>(rb);
-  xf_exchange_bc<NW>(wave, lane, lds, rb, ra);
+  xf_exchange_ab(wave, lane, lds, ra, rb);
+  xf_pass_b<32, 0>(rb);
+  xf_exchange_bc(wave, lane, lds, rb, ra);
   const uint32_t mine = (mask >> (8 * wave)) & 0xFFu;  // this wave's coding shards
   if (__builtin_amdgcn_ballot_w64(mine != 0) == 0) return;
-  xf_pass_c<NW, 0>(wave, ra);
+  xf_pass_c<0>(wave, ra);
   uint8_t* out = p.cw + g.off + 32ull * g.S;
   static_for<8>([&](auto T) {
     constexpr int t = decltype(T)::value;
@@ -336,28 +335,13 @@ __global__ __launch_bounds__(256, 2) void var_encode_kernel(const VarParams p) {
 
 // ---- W = 64 window decode over the column table ----------------------------------------
 
-__device__ __forceinline__ void var_lds_get_xor(const uint4* lds, int slot, int lane, uint32_t* v) {
-  static_for<4>([&](auto Q) {
-    constexpr int q = decltype(Q)::value;
-    const uint4 x = lds[(slot * 4 + q) * kXfLanes + lane];
-    v[4 * q] ^= x.x;
-    v[4 * q + 1] ^= x.y;
-    v[4 * q + 2] ^= x.z;
-    v[4 * q + 3] ^= x.w;
-  });
-}
-
-// decode_h8_kernel<-1, 0, 0, 0> (rs_kernels.hip: layouts A .. E, the swaps' epoch flags, the
+// decode_h8_kernel<-1, 0, 0, 0> (rs_window.hip: layouts A .. E, the swaps' epoch flags, the
 // formal derivative) for HighRate 32:32 with the fused coding restore: window position j < 32
 // is coding shred j, 32 + i data shred i.  32-column tiles; lanes l and l + 32 hold column
 // l & 31.  pmask [slice][2]: positions loaded, positions restored; rows [slice][64]: the
 // polynomial-basis locator constants (decode_rows_kernel), staged in LDS for the <= 32 slices
 // of the tile.
 __global__ __launch_bounds__(512, 4) void var_decode_kernel(const VarParams p) {
-  using LB = X8Lay<2, 1, 3, 4, 5>;
-  using LC = X8Lay<2, 3, 1, 4, 5>;
-  using LD = X8Lay<4, 3, 1, 2, 5>;
-  using LE = X8Lay<4, 5, 1, 2, 3>;
   constexpr int W = 64, kCols = 32;
   __shared__ uint4 lds[16 * 4 * kXfLanes];  // 8 waves x 2 slots x 4 KiB
   __shared__ X8Flags flags;
@@ -442,7 +426,7 @@ __global__ __launch_bounds__(512, 4) void var_decode_kernel(const VarParams p) {
       if (!((wave >> b) & 1)) {
         const int pw = wave | (1 << b);
         x8_wait_ge(&flags.ready[pw], e);
-        static_for<2>([&](auto U) { var_lds_get_xor(lds, 2 * pw + decltype(U)::value, lane, r[2 * rho + decltype(U)::value]); });
+        static_for<2>([&](auto U) { lds_get_xor(lds, 2 * pw + decltype(U)::value, lane, r[2 * rho + decltype(U)::value]); });
       }
     });
     x8_signal(&flags.done[wave], e, lane);

@@ -1,6 +1,7 @@
-// Device building blocks of the bitsliced transform kernels, shared by rs_kernels.hip
-// (xform / xform8 / decode_x) and rs_decode_c.hip (the correction decoder): tile I/O, the
-// pass A / B / C butterfly layers of xform<NW>, LDS exchanges, and the xform8 layouts and
+// Device building blocks of the bitsliced transform kernels, shared by rs_tile64.hip (xform /
+// xform8, decode_x / decode_x16, the per-call server), rs_window.hip (decode_h8 / decode_pk),
+// rs_xform64.hip (xform_h8), rs_var.hip and rs_decode_c.hip (the correction decoder): tile I/O, the
+// pass A / B / C butterfly layers of xform_kernel, LDS exchanges, and the xform8 layouts and
 // pairwise slot swaps.  gfx950 / CDNA4 only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -17,14 +18,12 @@ namespace {
 using dev::static_for;
 
 // =====================================================================================
-// xform<NW>: N = 8 * NW point transform (NW = 4 -> 32, NW = 8 -> 64); NW waves x 64
-// lanes; lane = one 64-byte column (32 symbols) of one block, each lane owns 8 of the N
-// shards in each of three passes:
+// xform: the 32-point transform on 4 waves x 64 lanes; lane = one 64-byte column (32
+// symbols) of one block, each lane owns 8 of the 32 shards in each of three passes:
 //   pass A  (wave w: shards 8w+t)       IFFT layers dist 1, 2, 4        (skew delta DIN)
-//   pass B  (wave w: shards w+NW*t)     IFFT dist 8 .. N/2; FFT N/2 .. 8 (DIN / DOUT)
+//   pass B  (wave w: shards w+4t)       IFFT dist 8, 16; FFT 16, 8      (DIN / DOUT)
 //   pass C  (wave w: shards 8w+t)       FFT layers dist 4, 2, 1         (skew delta DOUT)
-// Shards change owner between passes through LDS (2 rounds per exchange: 64 KiB per
-// round for N = 32, 128 KiB for N = 64).
+// Shards change owner between passes through LDS (2 rounds of 64 KiB per exchange).
 // Skew index of a layer of distance d on the group starting at g: g + d + delta - 1.
 // In pass B the group start depends only on shard bits >= 4, i.e. on the slot index, so
 // that code is wave-independent; passes A and C branch once per butterfly on the
@@ -40,99 +39,82 @@ template <int S, bool INV>
 __device__ __forceinline__ void bfly(uint32_t* x, uint32_t* y) {
   if constexpr (INV) dev::ifft_bfly<S>(x, y); else dev::fft_bfly<S>(x, y);
 }
-template <int BASE, bool INV, int NW>
+template <int BASE, bool INV>
 __device__ __forceinline__ void bfly_w(int wave, uint32_t* x, uint32_t* y) {
-  if constexpr (NW == 4) {
-    switch (wave) {
-      case 0: bfly<BASE, INV>(x, y); break;
-      case 1: bfly<BASE + 8, INV>(x, y); break;
-      case 2: bfly<BASE + 16, INV>(x, y); break;
-      default: bfly<BASE + 24, INV>(x, y); break;
-    }
-  } else {
-    switch (wave) {
-      case 0: bfly<BASE, INV>(x, y); break;
-      case 1: bfly<BASE + 8, INV>(x, y); break;
-      case 2: bfly<BASE + 16, INV>(x, y); break;
-      case 3: bfly<BASE + 24, INV>(x, y); break;
-      case 4: bfly<BASE + 32, INV>(x, y); break;
-      case 5: bfly<BASE + 40, INV>(x, y); break;
-      case 6: bfly<BASE + 48, INV>(x, y); break;
-      default: bfly<BASE + 56, INV>(x, y); break;
-    }
+  switch (wave) {
+    case 0: bfly<BASE, INV>(x, y); break;
+    case 1: bfly<BASE + 8, INV>(x, y); break;
+    case 2: bfly<BASE + 16, INV>(x, y); break;
+    default: bfly<BASE + 24, INV>(x, y); break;
   }
 }
-template <int NW, int DIN>
+template <int DIN>
 __device__ __forceinline__ void xf_pass_a(int wave, Regs8& r) {
   static_for<4>([&](auto I) {  // dist 1
     constexpr int t = 2 * decltype(I)::value;
-    bfly_w<t + 1 + DIN - 1, true, NW>(wave, r[t], r[t + 1]);
+    bfly_w<t + 1 + DIN - 1, true>(wave, r[t], r[t + 1]);
   });
   static_for<4>([&](auto I) {  // dist 2
     constexpr int g = 4 * (decltype(I)::value >> 1);
     constexpr int u = g + (decltype(I)::value & 1);
-    bfly_w<g + 2 + DIN - 1, true, NW>(wave, r[u], r[u + 2]);
+    bfly_w<g + 2 + DIN - 1, true>(wave, r[u], r[u + 2]);
   });
   static_for<4>([&](auto I) {  // dist 4
     constexpr int u = decltype(I)::value;
-    bfly_w<4 + DIN - 1, true, NW>(wave, r[u], r[u + 4]);
+    bfly_w<4 + DIN - 1, true>(wave, r[u], r[u + 4]);
   });
 }
 
-// Pass B: slot t holds shard w + NW*t.  Layer on shard bit sb (dist 2^sb, sb >= 3) pairs
-// slots t, t + 2^tb with tb = sb - log2(NW); group start (NW*t) & ~(2d - 1).
-template <int NW>
+// Pass B: slot t holds shard w + 4t.  Layer on shard bit sb (dist 2^sb, sb = 3, 4) pairs
+// slots t, t + 2^tb with tb = sb - 2; group start (4t) & ~(2d - 1).
 struct PassB {
-  static constexpr int kLogNw = NW == 4 ? 2 : 3;
-  static constexpr int kLayers = NW == 4 ? 2 : 3;  // shard bits 3 .. 3 + kLayers - 1
+  static constexpr int kLayers = 2;  // shard bits 3, 4
   template <int L, int I>
   struct Pair {
-    static constexpr int sb = 3 + L, tb = sb - kLogNw, d = 1 << sb;
+    static constexpr int sb = 3 + L, tb = sb - 2, d = 1 << sb;
     static constexpr int t = ((I >> tb) << (tb + 1)) | (I & ((1 << tb) - 1));
     static constexpr int u = t + (1 << tb);
-    static constexpr int g = (NW * t) & ~(2 * d - 1);
+    static constexpr int g = (4 * t) & ~(2 * d - 1);
   };
 };
-template <int NW, int DIN>
+template <int DIN>
 __device__ __forceinline__ void xf_pass_b_ifft(Regs8& r) {
-  constexpr int NL = PassB<NW>::kLayers;
-  static_for<NL>([&](auto L) {  // ascending distance
+  static_for<PassB::kLayers>([&](auto L) {  // ascending distance
     static_for<4>([&](auto I) {
-      using P = typename PassB<NW>::template Pair<decltype(L)::value, decltype(I)::value>;
+      using P = PassB::Pair<decltype(L)::value, decltype(I)::value>;
       dev::ifft_bfly<P::g + P::d + DIN - 1>(r[P::t], r[P::u]);
     });
   });
 }
-template <int NW, int DOUT>
+template <int DOUT>
 __device__ __forceinline__ void xf_pass_b_fft(Regs8& r) {
-  constexpr int NL = PassB<NW>::kLayers;
-  static_for<NL>([&](auto L) {  // descending distance
+  static_for<PassB::kLayers>([&](auto L) {  // descending distance
     static_for<4>([&](auto I) {
-      using P = typename PassB<NW>::template Pair<NL - 1 - decltype(L)::value, decltype(I)::value>;
+      using P = PassB::Pair<PassB::kLayers - 1 - decltype(L)::value, decltype(I)::value>;
       dev::fft_bfly<P::g + P::d + DOUT - 1>(r[P::t], r[P::u]);
     });
   });
 }
-template <int NW, int DIN, int DOUT>
+template <int DIN, int DOUT>
 __device__ __forceinline__ void xf_pass_b(Regs8& r) {
-  xf_pass_b_ifft<NW, DIN>(r);
-  xf_pass_b_fft<NW, DOUT>(r);
+  xf_pass_b_ifft<DIN>(r);
+  xf_pass_b_fft<DOUT>(r);
 }
 
-template <int NW, int DOUT>
+template <int DOUT>
 __device__ __forceinline__ void xf_pass_c(int wave, Regs8& r) {
   static_for<4>([&](auto I) {  // dist 4
     constexpr int u = decltype(I)::value;
-    bfly_w<4 + DOUT - 1, false, NW>(wave, r[u], r[u + 4]);
+    bfly_w<4 + DOUT - 1, false>(wave, r[u], r[u + 4]);
   });
   static_for<4>([&](auto I) {  // dist 2
     constexpr int g = 4 * (decltype(I)::value >> 1);
     constexpr int u = g + (decltype(I)::value & 1);
-    bfly_w<g + 2 + DOUT - 1, false, NW>(wave, r[u], r[u + 2]);
+    bfly_w<g + 2 + DOUT - 1, false>(wave, r[u], r[u + 2]);
   });
   static_for<4>([&](auto I) {  // dist 1
     constexpr int t = 2 * decltype(I)::value;
-    bfly_w<t + 1 + DOUT - 1, false, NW>(wave, r[t], r[t + 1]);
+    bfly_w<t + 1 + DOUT - 1, false>(wave, r[t], r[t + 1]);
   });
 }
 
@@ -150,6 +132,16 @@ __device__ __forceinline__ void lds_get(const uint4* lds, int slot, int lane, ui
     v[4 * q + 1] = x.y;
     v[4 * q + 2] = x.z;
     v[4 * q + 3] = x.w;
+  });
+}
+__device__ __forceinline__ void lds_get_xor(const uint4* lds, int slot, int lane, uint32_t* v) {
+  static_for<4>([&](auto Q) {
+    constexpr int q = decltype(Q)::value;
+    const uint4 x = lds[(slot * 4 + q) * kXfLanes + lane];
+    v[4 * q] ^= x.x;
+    v[4 * q + 1] ^= x.y;
+    v[4 * q + 2] ^= x.z;
+    v[4 * q + 3] ^= x.w;
   });
 }
 
@@ -560,10 +552,8 @@ __device__ __forceinline__ void store_shard(uint8_t* __restrict__ base, const Ti
   });
 }
 
-// LDS exchange between passes (2 rounds, 4 A-slots per wave per round).
-//   NW = 4: A-slot t of wave w (shard 8w+t) <-> B-slot 2w+(t>>2) of wave t&3
-//   NW = 8: A-slot t of wave w (shard 8w+t) <-> B-slot w of wave t
-template <int NW>
+// LDS exchange between passes (2 rounds, 4 A-slots per wave per round):
+// A-slot t of wave w (shard 8w+t) <-> B-slot 2w+(t>>2) of wave t&3
 __device__ __forceinline__ void xf_exchange_ab(int wave, int lane, uint4* lds, Regs8& ra, Regs8& rb) {
   static_for<2>([&](auto Rho) {
     constexpr int rho = decltype(Rho)::value;
@@ -572,40 +562,21 @@ __device__ __forceinline__ void xf_exchange_ab(int wave, int lane, uint4* lds, R
       lds_put(lds, 4 * wave + u, lane, ra[4 * rho + u]);
     });
     __syncthreads();
-    if constexpr (NW == 4) {
-      static_for<4>([&](auto W2) {
-        constexpr int w2 = decltype(W2)::value;
-        lds_get(lds, 4 * w2 + wave, lane, rb[2 * w2 + rho]);
-      });
-    } else {
-      if ((wave >> 2) == rho) {
-        static_for<8>([&](auto W2) {
-          constexpr int w2 = decltype(W2)::value;
-          lds_get(lds, 4 * w2 + (wave & 3), lane, rb[w2]);
-        });
-      }
-    }
+    static_for<4>([&](auto W2) {
+      constexpr int w2 = decltype(W2)::value;
+      lds_get(lds, 4 * w2 + wave, lane, rb[2 * w2 + rho]);
+    });
     __syncthreads();
   });
 }
 
-template <int NW>
 __device__ __forceinline__ void xf_exchange_bc(int wave, int lane, uint4* lds, Regs8& rb, Regs8& ra) {
   static_for<2>([&](auto Rho) {
     constexpr int rho = decltype(Rho)::value;
-    if constexpr (NW == 4) {
-      static_for<4>([&](auto W2) {
-        constexpr int w2 = decltype(W2)::value;
-        lds_put(lds, 4 * w2 + wave, lane, rb[2 * w2 + rho]);
-      });
-    } else {
-      if ((wave >> 2) == rho) {
-        static_for<8>([&](auto W2) {
-          constexpr int w2 = decltype(W2)::value;
-          lds_put(lds, 4 * w2 + (wave & 3), lane, rb[w2]);
-        });
-      }
-    }
+    static_for<4>([&](auto W2) {
+      constexpr int w2 = decltype(W2)::value;
+      lds_put(lds, 4 * w2 + wave, lane, rb[2 * w2 + rho]);
+    });
     __syncthreads();
     static_for<4>([&](auto U) {
       constexpr int u = decltype(U)::value;
@@ -643,10 +614,10 @@ __device__ __forceinline__ uint32_t qmask_all(const TileIO& io, const uint64_t* 
 
 // =====================================================================================
 // xform8: the 32-point transform with 8 waves per workgroup and 4 shard slots per lane.
-// Half the per-lane state of xform<4> (16 loads per lane in flight instead of 32, ~half
+// Half the per-lane state of xform_kernel (16 loads per lane in flight instead of 32, ~half
 // the VGPRs), so two 8-wave workgroups share a CU and each wave has half the arithmetic
 // between its loads and its stores (tools/membench/membench4.hip: 64-column tile copies
-// 5.57 -> 5.74 TB/s at 8 waves; xform<4> runs at its own load/store skeleton's speed).
+// 5.57 -> 5.74 TB/s at 8 waves; xform_kernel runs at its own load/store skeleton's speed).
 // Every position bit is a slot bit (2) or a wave bit (3), so a layer's skew constant
 // depends only on slot bits (compile time) and wave bits (a scalar switch over the wave
 // bits above the layer).  A layer needs its bit in a slot; between layers one slot bit
@@ -806,10 +777,10 @@ __device__ __forceinline__ void x8_layer_lay(int wave, Regs4& r) {
 // (which would send the whole slot array to scratch).
 // Partner waves synchronise through LDS epoch flags instead of workgroup barriers (ready[w] =
 // last swap whose data w has written, done[w] = last swap w has read).
-template <int NWAVES>
+template <int WAVES>
 struct XFlags {
-  uint32_t ready[NWAVES];
-  uint32_t done[NWAVES];
+  uint32_t ready[WAVES];
+  uint32_t done[WAVES];
 };
 using X8Flags = XFlags<8>;
 __device__ __forceinline__ void x8_wait_ge(const uint32_t* f, uint32_t e) {
@@ -899,6 +870,28 @@ __device__ __forceinline__ void h8_relayout(Regs4& r) {
     });
   });
 }
+
+// ---- the 64-point pipeline on 32-column tiles ------------------------------------------
+// What decode_h8, decode_pk, var_decode and xform_h8 run between their own loads / products and
+// their own store predicates / stores.  Each kernel writes the sequence out itself: with the
+// IFFT, the derivative and the FFT lifted into shared __forceinline__ templates every one of
+// them compiled to different instructions and register counts (a helper is optimised on its own
+// before it is inlined), so a change to the hand-over protocol has to be made in all four.
+// Layouts (slot bits | lane half | wave bits); A <-> B is h8_relayout, every other step an
+// x8_swap:
+//   A  slots p0 p1 | h p2 | waves p3 p4 p5   IFFT b0; FFT b0
+//   B  slots p2 p1 | h p0 | waves p3 p4 p5   IFFT b1 b2 / FFT b1
+//   C  slots p2 p3 | h p0 | waves p1 p4 p5   IFFT b3 / FFT b2
+//   D  slots p4 p3 | h p0 | waves p1 p2 p5   IFFT b4 / FFT b3
+//   E  slots p4 p5 | h p0 | waves p1 p2 p3   IFFT b5, formal derivative, FFT b5 b4
+// The 64 KiB buffer is handed over by the swaps' epoch flags, with no workgroup barrier (ready =
+// published, done = this wave's reads finished; a region is rewritten once every reader of its
+// last epoch is done).  Epochs: IFFT swaps 1-3, derivative rounds 4-5, FFT swaps 4 + D .. 6 + D
+// (D = 2 after a derivative, else 0).
+using LB = X8Lay<2, 1, 3, 4, 5>;
+using LC = X8Lay<2, 3, 1, 4, 5>;
+using LD = X8Lay<4, 3, 1, 2, 5>;
+using LE = X8Lay<4, 5, 1, 2, 3>;
 
 // Lane-linear I/O for 32-column tiles (xform_h8): in each half (lanes 0..31, 32..63: two
 // positions) lane i reads quarter i & 3 of chunk (i >> 2) + 8 q with instruction q, so every

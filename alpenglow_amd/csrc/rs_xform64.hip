@@ -43,10 +43,6 @@ using dev::static_for;
 // once and its IFFT computed once for both chunks.
 template <int DIN, int DOUT, bool HALF = false, bool LR2 = false>
 __global__ __launch_bounds__(512, 4) void xform_h8_kernel(const XformParams p) {
-  using LB = X8Lay<2, 1, 3, 4, 5>;
-  using LC = X8Lay<2, 3, 1, 4, 5>;
-  using LD = X8Lay<4, 3, 1, 2, 5>;
-  using LE = X8Lay<4, 5, 1, 2, 3>;
   __shared__ uint4 lds[16 * 4 * kXfLanes];  // 8 waves x 2 slots x 4 KiB
   __shared__ X8Flags flags;
   const int lane = threadIdx.x & 63;

@@ -46,9 +46,9 @@ def _c(row, k, m, S, n, patterns="one", layout=PLAIN):
 
 
 CASES = [
-    # 1: decode_x<4> (W = 32), one pattern
+    # 1: decode_x (W = 32), one pattern
     _c(1, 16, 4, 192, 7), _c(1, 16, 16, 64, 70, layout=PADS), _c(1, 24, 8, 4096, 3),
-    # 2: decode_x<4>, per block (S / 64 % 64 == 0; block_ids: some blocks restore nothing)
+    # 2: decode_x, per block (S / 64 % 64 == 0; block_ids: some blocks restore nothing)
     _c(2, 16, 4, 4096, 6, "per_block"), _c(2, 24, 8, 4096, 5, "per_block", PADS),
     # 3: decode_x<4, per lane>
     _c(3, 16, 4, 192, 23, "per_block"), _c(3, 24, 8, 64, 70, "per_block", PADS), _c(3, 13, 4, 128, 9, "per_block"),

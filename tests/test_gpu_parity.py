@@ -113,8 +113,8 @@ def test_fast_encode_many_blocks(ctx, dev, S, n):
 ])
 def test_headline_encode_dispatch(ctx, dev, S, n, kernel):
     """32:32 device-resident encodes of at least 256 tiles (64-column tiles): the headline
-    kernel xform<4> and the 8 / 16 KiB-shard rule that sends those to xform8
-    (launch_xform, rs_kernels.hip) against the C oracle, asserting which kernel ran."""
+    kernel xform_kernel and the 8 / 16 KiB-shard rule that sends those to xform8
+    (launch_xform, rs_tile64.hip) against the C oracle, asserting which kernel ran."""
     tiles = n * (S // 64) // 64
     assert tiles >= 256
     blocks = _blocks(7100 + S, n, 32, S)
@@ -1273,7 +1273,7 @@ def test_tail_chunk_encode_decode(ctx, dev, k, m, S):
 def test_tail_chunks_in_kernel(ctx, dev, S, n, k):
     """32-point geometries whose shards end in the crate's split tail chunk (S mod 64 != 0):
     encode and the full-recovery reconstruct read and write the tail in place (the TAIL
-    transforms: xform<4> at >= 256 tiles, xform8 below; rs_xform.hpp tile_io_g), no restride
+    transforms: xform_kernel at >= 256 tiles, xform8 below; rs_xform.hpp tile_io_g), no restride
     (tails under 16 bytes still restride).
     Tails of T = 2..62 bytes (odd and even halves), against the C oracle and the originals;
     per-block random erasures (and erasures confined to shards 0..15: the pruned FFT).  S =

@@ -167,7 +167,7 @@ def _walsh_mod(v):
 
 @pytest.mark.parametrize("N,W", [(64, 64), (64, 32), (64, 16), (128, 128)])
 def test_window_locator_walsh_route(N, W):
-    """decode_rows / decode_rows128 (rs_kernels.hip): loc(x) = sum_{e erased, e != x} log(x ^ e)
+    """decode_rows / decode_rows128 (rs_window.hip): loc(x) = sum_{e erased, e != x} log(x ^ e)
     mod 65535 as the XOR convolution of L (L(z) = log z, L(0) = 0, zero past W) with the
     erasure indicator, i.e. H(H(L) * H(I)) / N over Z/65535 (N^-1 = 1024 / 512 since 2^16 = 1),
     against the loop form; the constants exp[loc] then agree bit for bit (exp[65535] = exp[0])."""
@@ -190,7 +190,7 @@ def test_window_locator_walsh_route(N, W):
 
 
 def test_poly_basis_powers():
-    """The per-call server's locator (rs_kernels.hip PkLocTables, poly_pow_a) computes a
+    """The per-call server's locator (rs_decode_pk.hpp PkLocTables, poly_pow_a) computes a
     decoder constant to_poly(exp[l]) as a^l in GF(2)[a] / (a^16 + a^5 + a^3 + a^2 + 1), from
     the tables a^i and a^(256 i): to_poly (the basis map of rs_device.hpp, kBasisMat[0] of the
     generated rs_consts.inc) sends exp[l] to the l-th power of the polynomial generator for
@@ -425,7 +425,7 @@ def test_avx2_engine_matches_scalar_oracle(k, m, S):
 
 @pytest.mark.parametrize("seed", range(4))
 def test_window128_two_pass_split(seed):
-    """The identity decode_x16's W = 128 passes rely on (rs_kernels.hip decode_x16 PASS 1/2):
+    """The identity decode_x16's W = 128 passes rely on (rs_window.hip decode_x16 PASS 1/2):
     the crate decoder's IFFT_128 -> formal derivative -> FFT_128 equals, per output half o,
     FFT_64 (skew delta 64 o) of P(u_o) ^ u_(1-o), where u_h = IFFT_64 of window half h (delta
     64 h) and P = the derivative without its self term -- because the size-128 layer's skew

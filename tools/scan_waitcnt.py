@@ -149,7 +149,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=int, default=1)
     ap.add_argument("--verbose", action="store_true")
-    ap.add_argument("srcs", nargs="*", default=["rs_kernels.hip", "rs_xform64.hip", "rs_decode_c.hip"])
+    ap.add_argument("srcs", nargs="*", default=["rs_tile64.hip", "rs_window.hip", "rs_generic.hip", "rs_coder_kernels.hip",
+                                                 "rs_xform64.hip", "rs_decode_c.hip"])
     args = ap.parse_args()
     total = 0
     with tempfile.TemporaryDirectory() as d:
