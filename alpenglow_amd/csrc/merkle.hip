@@ -169,16 +169,31 @@ __global__ __launch_bounds__(256) void merkle_leaf_kernel(const MerkleBuildParam
 // One loader serves both: kLeafU16 issues the aligned path's global_load_dwordx4 / _dword at
 // whatever address the row has (an aligned row costs what it costs in merkle_leaf_kernel<true>;
 // a straddling access is split by the memory pipeline, not by byte loads in the shader).
-__global__ __launch_bounds__(256) void merkle_leaf_var_kernel(const MerkleBuildParams p, uint8_t* nodes,
-                                                              uint64_t nodes_stride) {
+// FLAGGED: only the leaves with p.hash_leaf[64 s + j] != 0 (a deshred's rebuild: the other leaves'
+// digests are already in nodes).  Still one wave per slice, so the size stays wave-uniform; the
+// lanes of kept leaves idle.
+template <bool FLAGGED>
+__device__ __forceinline__ void merkle_leaf_var_body(const MerkleBuildParams& p, uint8_t* nodes,
+                                                     uint64_t nodes_stride) {
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint64_t s = static_cast<uint64_t>(blockIdx.x) * 4 + wave;
   if (s >= p.nslices) return;
   const uint32_t j = threadIdx.x & 63;
   const uint32_t len = __builtin_amdgcn_readfirstlane(p.leaf_sizes[s]);
+  if constexpr (FLAGGED) {
+    if (!p.hash_leaf[s * kMerkleMaxLeaves + j]) return;
+  }
   uint32_t h[8];
   leaf_hash<kLeafU16>(p.leaves + s * p.slice_stride + static_cast<uint64_t>(j) * len, len, h);
   store_digest(nodes + s * nodes_stride + 32 * j, h);
+}
+__global__ __launch_bounds__(256) void merkle_leaf_var_kernel(const MerkleBuildParams p, uint8_t* nodes,
+                                                              uint64_t nodes_stride) {
+  merkle_leaf_var_body<false>(p, nodes, nodes_stride);
+}
+__global__ __launch_bounds__(256) void merkle_leaf_var_flagged_kernel(const MerkleBuildParams p, uint8_t* nodes,
+                                                                      uint64_t nodes_stride) {
+  merkle_leaf_var_body<true>(p, nodes, nodes_stride);
 }
 
 __global__ __launch_bounds__(256) void merkle_level_kernel(const MerkleBuildParams p, uint8_t* nodes,
@@ -237,8 +252,11 @@ __global__ __launch_bounds__(256) void merkle_proof_kernel(const MerkleBuildPara
 // when roots_out is set.
 // LIST: thread i verifies leaf list[i] for i < list[n] (the compacted active leaves).
 // ITEM: per-item proof length and the check_proof_last rule (proof_len / last; check mode only).
-template <bool A4, bool LIST, bool ITEM = false>
-__global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyParams p) {
+// VAR (p.leaf_sizes set; derive-root mode): leaf t is leaf_sizes[t / size_group] bytes -- size_group
+// 1: at t * leaf_stride (gathered rows); 64: row t % 64 of slice t / 64, packed at that size from
+// the slice's group_stride.  Rows are 2-byte aligned: the kLeafU16 loader.
+template <bool A4, bool LIST, bool ITEM, bool VAR>
+__device__ __forceinline__ void merkle_verify_body(const MerkleVerifyParams& p) {
   uint64_t t = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if constexpr (LIST) {
     if (t >= p.list[p.n]) return;
@@ -247,7 +265,14 @@ __global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyPa
     if (t >= p.n || (p.active && !p.active[t])) return;
   }
   uint32_t node[8];
-  leaf_hash<A4>(p.leaves + grouped_row_offset(t, p.leaf_stride, p.group_stride, p.skip_row), p.leaf_bytes, node);
+  if constexpr (VAR) {
+    const uint64_t g = t / p.size_group;
+    const uint32_t len = p.leaf_sizes[g];
+    const uint64_t off = p.size_group == 1 ? t * p.leaf_stride : g * p.group_stride + (t - g * p.size_group) * len;
+    leaf_hash<kLeafU16>(p.leaves + off, len, node);
+  } else {
+    leaf_hash<A4>(p.leaves + grouped_row_offset(t, p.leaf_stride, p.group_stride, p.skip_row), p.leaf_bytes, node);
+  }
   if (p.leaf_nodes)
     store_digest(p.leaf_nodes + (t / p.leaves_per_tree) * p.leaf_nodes_stride + 32 * (t % p.leaves_per_tree), node);
   uint32_t idx = p.index[t];
@@ -291,6 +316,14 @@ __global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyPa
 #pragma unroll
   for (int i = 0; i < 8; ++i) ok = ok && node[i] == root[i];
   p.ok[t] = ok ? 1 : 0;
+}
+template <bool A4, bool LIST, bool ITEM = false>
+__global__ __launch_bounds__(256) void merkle_verify_kernel(const MerkleVerifyParams p) {
+  merkle_verify_body<A4, LIST, ITEM, false>(p);
+}
+template <bool LIST>
+__global__ __launch_bounds__(256) void merkle_verify_var_kernel(const MerkleVerifyParams p) {
+  merkle_verify_body<false, LIST, false, true>(p);
 }
 
 // list[0 .. *count) = the t < n with active[t] != 0 (in no particular order): per 1024-thread
@@ -463,13 +496,16 @@ hipError_t launch_merkle_build(const MerkleBuildParams& p, uint8_t* nodes, uint6
                                hipStream_t stream, uint32_t* leaf_kernels) {
   if (p.nslices == 0) return hipSuccess;
   if (p.n_leaves == 0 || p.n_leaves > kMerkleMaxLeaves || !nodes || nodes_stride % 16) return hipErrorInvalidValue;
-  if (p.leaf_sizes && (p.n_leaves != kMerkleMaxLeaves || p.hash_leaf || p.skip_leaf)) return hipErrorInvalidValue;
+  if (p.leaf_sizes && (p.n_leaves != kMerkleMaxLeaves || p.skip_leaf)) return hipErrorInvalidValue;
   auto grid_of = [](uint64_t threads) { return dim3(static_cast<unsigned>((threads + 255) / 256)); };
   if ((p.nslices * p.n_leaves + 255) / 256 > 0x7FFFFFFFull) return hipErrorInvalidValue;
   const bool a16 = (reinterpret_cast<uintptr_t>(p.leaves) | p.leaf_stride | p.slice_stride) % 16 == 0;
   const dim3 g0 = grid_of(p.nslices * p.n_leaves);
-  if (leaf_kernels) *leaf_kernels |= p.leaf_sizes ? kMkLeafVar : a16 ? kMkLeafAligned : kMkLeafByte;
-  if (p.leaf_sizes) {  // (g0: four waves, four slices, per workgroup)
+  if (leaf_kernels)
+    *leaf_kernels |= p.leaf_sizes ? (p.hash_leaf ? kMkLeafVarFlagged : kMkLeafVar) : a16 ? kMkLeafAligned : kMkLeafByte;
+  if (p.leaf_sizes && p.hash_leaf) {  // (no compaction: one wave per slice keeps the size wave-uniform)
+    hipLaunchKernelGGL(merkle_leaf_var_flagged_kernel, g0, dim3(256), 0, stream, p, nodes, nodes_stride);
+  } else if (p.leaf_sizes) {  // (g0: four waves, four slices, per workgroup)
     hipLaunchKernelGGL(merkle_leaf_var_kernel, g0, dim3(256), 0, stream, p, nodes, nodes_stride);
   } else if (p.hash_leaf && p.list) {  // only the flagged leaves: compacted, so no lane idles on a known one
     const uint64_t nl = p.nslices * p.n_leaves;
@@ -511,6 +547,20 @@ hipError_t launch_merkle_verify(const MerkleVerifyParams& p, hipStream_t stream)
     return hipGetLastError();
   }
   if (p.last) return hipErrorInvalidValue;
+  if (p.leaf_sizes) {  // one leaf size per group of items: derive-root mode only
+    if (!p.roots_out || p.skip_row ||
+        (p.size_group != 1 && (p.size_group != kMerkleMaxLeaves || !p.group_stride || p.n % kMerkleMaxLeaves)))
+      return hipErrorInvalidValue;
+    if (p.active && p.list && p.n < 0xFFFFFFFFull) {
+      if (hipMemsetAsync(p.list + p.n, 0, 4, stream) != hipSuccess) return hipErrorInvalidValue;
+      hipLaunchKernelGGL(compact_active_kernel, dim3(static_cast<unsigned>((p.n + 1023) / 1024)), dim3(1024), 0,
+                         stream, p.active, p.n, p.list + p.n, p.list);
+      hipLaunchKernelGGL(merkle_verify_var_kernel<true>, grid, dim3(256), 0, stream, p);
+    } else {
+      hipLaunchKernelGGL(merkle_verify_var_kernel<false>, grid, dim3(256), 0, stream, p);
+    }
+    return hipGetLastError();
+  }
   if (p.active && p.list && p.n < 0xFFFFFFFFull) {
     if (hipMemsetAsync(p.list + p.n, 0, 4, stream) != hipSuccess) return hipErrorInvalidValue;
     hipLaunchKernelGGL(compact_active_kernel, dim3(static_cast<unsigned>((p.n + 1023) / 1024)), dim3(1024), 0, stream,

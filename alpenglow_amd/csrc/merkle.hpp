@@ -44,9 +44,11 @@ struct MerkleBuildParams {
   uint32_t* list;
   uint32_t skip_leaf;  // > 0: leaf j >= skip_leaf sits at (j + 1) * leaf_stride (a withheld row)
   // nullable: one leaf size per slice (device [nslices], each even, 2 .. 1024).  Needs n_leaves =
-  // 64 and no hash_leaf / skip_leaf; leaf j of slice s is then leaf_sizes[s] bytes at leaves +
+  // 64 and no skip_leaf; leaf j of slice s is then leaf_sizes[s] bytes at leaves +
   // s*slice_stride + j*leaf_sizes[s] (the var coder's packed codewords); leaf_stride and
   // leaf_bytes are unused.  One leaf kernel for the whole batch, whatever the mix of sizes.
+  // With hash_leaf: only the flagged leaves, one wave per slice (list unused: no compaction, the
+  // size stays wave-uniform).
   const uint32_t* leaf_sizes;
 };
 // The leaf kernel classes a build launches (leaf_kernels below; a test aid).
@@ -54,6 +56,7 @@ enum MerkleLeafKernelBit : uint32_t {
   kMkLeafAligned = 1u << 0,  // uniform size, every row 16-byte aligned: vector loads
   kMkLeafByte = 1u << 1,     // uniform size, any alignment: the per-byte loader
   kMkLeafVar = 1u << 2,      // one size per slice (leaf_sizes)
+  kMkLeafVarFlagged = 1u << 3,  // one size per slice, only the flagged leaves (leaf_sizes + hash_leaf)
 };
 // nodes: the node digests (reference order, nodes_stride per slice; the caller's buffer or
 // scratch) -- the levels are built there.  leaf_kernels (nullable): |= the MerkleLeafKernelBit of
@@ -91,6 +94,12 @@ struct MerkleVerifyParams {
   const uint32_t* proof_len;
   const uint8_t* last;
   const uint32_t* empty_roots;  // device [32][8] big-endian words
+  // nullable (derive-root mode with active + list): one leaf size per size_group consecutive items
+  // (device [n / size_group], each even, 2 .. 1024) instead of leaf_bytes.  size_group 1: leaf t
+  // at leaves + t*leaf_stride; size_group 64: leaf t is row t % 64 of slice t / 64, at leaves +
+  // (t / 64)*group_stride + (t % 64)*size (rows packed at the slice's size; no skip_row)
+  const uint32_t* leaf_sizes;
+  uint32_t size_group;
 };
 hipError_t launch_merkle_verify(const MerkleVerifyParams& p, hipStream_t stream);
 

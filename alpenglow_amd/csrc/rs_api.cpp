@@ -1642,7 +1642,10 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
                         const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
                         const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
                         uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes, size_t leaf_nodes_stride,
-                        uint32_t leaves_per_tree, size_t group_stride, uint32_t skip_row, bool roots_ready) {
+                        uint32_t leaves_per_tree, size_t group_stride, uint32_t skip_row, bool roots_ready,
+                        const uint32_t* leaf_sizes, uint32_t size_group) {
+  // leaf_sizes / size_group (device, nullable): one shred size per size_group consecutive shreds
+  // (MerkleVerifyParams; data_bytes then only bounds the sizes).
   // roots_ready: step 1 already ran (launch_derive_roots, e.g. on another stream): roots_out holds
   // every active shred's derived root
   if (roots_ready && !roots_out) return AG_RS_ERR_INVALID_ARGUMENT;
@@ -1688,6 +1691,8 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
   mp.leaves_per_tree = leaves_per_tree;
   mp.group_stride = group_stride;
   mp.skip_row = skip_row;
+  mp.leaf_sizes = leaf_sizes;
+  mp.size_group = size_group;
   if (!roots_ready && ag::launch_merkle_verify(mp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   // 2. SliceCommitment + cached-commitment rule (validated_shred.rs:57-64)
   AG_HIP(hipMemsetAsync(count, 0, 4, c->stream));
@@ -2111,6 +2116,49 @@ int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_
     return st;
   return pipe_coder_finish(c, n, plen);
 }
+// The device stages of ag_rs_coder_deshred_batch_var (32:32, ANY_K) over present words and the
+// size / column table already on the device (d_sizes[n], d_col_base[n + 1] with total_columns its
+// last entry): pipe_coder_enqueue's stages over the column table -- patterns and locator
+// constants (they do not depend on S), the window decode with the fused coding restore, the
+// strip, the store masks, and the re-encode when `reencode` (some slice has surplus shreds or
+// every data shred; otherwise every store mask is zero).  Synchronous: plen[s] on return.  The
+// caller has reset last_encode_kernels / last_window_kernels.
+int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                           const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
+                           bool reencode, int64_t* plen) {
+  int st;
+  if ((st = pipe_coder_reserve(c, n, kDataShreds))) return st;
+  uint64_t* xm = c->xmask.dev.as<uint64_t>();
+  uint32_t* rows = c->d_rows.as<uint32_t>();
+  uint8_t* few = c->d_pipe_few.as<uint8_t>();
+  uint64_t* mask = c->d_pipe_mask.as<uint64_t>();
+  int64_t* strip = c->d_strip.as<int64_t>();
+  if (ag::launch_pipe_patterns(d_present, n, xm, few, true, c->stream) != hipSuccess ||
+      ag::launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), 64, c->dtables(), rows, true, c->stream) !=
+          hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  ag::VarParams p{};
+  p.cw = cw;
+  p.stride = cw_stride;
+  p.sizes = d_sizes;
+  p.col_base = d_col_base;
+  p.nslices = static_cast<uint32_t>(n);
+  p.total_columns = total_columns;
+  p.pmask = xm + n;
+  p.rows = rows;
+  c->last_window_kernels |= ag::kDxVar;
+  if (ag::launch_var_decode(p, c->stream) != hipSuccess ||
+      ag::launch_var_strip(cw, cw_stride, d_sizes, n, strip, c->stream) != hipSuccess ||
+      ag::launch_pipe_store_masks(few, strip, d_present, 1, n, mask, -AG_RS_ERR_NOT_ENOUGH_SHARDS,
+                                  -AG_RS_ERR_INVALID_PADDING, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  if (reencode) {
+    p.out_mask = mask;
+    c->last_encode_kernels |= ag::kEkVar;
+    if (ag::launch_var_encode(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  }
+  return pipe_coder_finish(c, n, plen);
+}
 // shred sizes pipe_coder_deshred decodes on the device: whole 64-byte chunks (any m of the
 // device-pattern path), or for 32:32 a last chunk of T = S mod 64 bytes -- T >= 16 always, a
 // shorter T when no slice needs the re-encode (no_reencode: no surplus shreds, no slice with
@@ -2261,41 +2309,33 @@ int ag_rs_coder_deshred_batch_var(ag_rs_ctx* c, size_t m, size_t n, const uint32
   AG_HIP(hipEventRecord(c->present_ev, c->stream));
   const uint64_t* d_present = c->d_present.as<uint64_t>();
   const uint32_t* d = reinterpret_cast<const uint32_t*>(d_present + n);
-  // pipe_coder_enqueue's stages over the column table: patterns and locator constants (they do
-  // not depend on S), the window decode with the fused coding restore, the strip, the store
-  // masks, the re-encode
-  if ((st = pipe_coder_reserve(c, n, kDataShreds))) return st;
-  uint64_t* xm = c->xmask.dev.as<uint64_t>();
-  uint32_t* rows = c->d_rows.as<uint32_t>();
-  uint8_t* few = c->d_pipe_few.as<uint8_t>();
-  uint64_t* mask = c->d_pipe_mask.as<uint64_t>();
-  int64_t* strip = c->d_strip.as<int64_t>();
-  if (ag::launch_pipe_patterns(d_present, n, xm, few, true, c->stream) != hipSuccess ||
-      ag::launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), 64, c->dtables(), rows, true, c->stream) !=
-          hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  ag::VarParams p{};
-  p.cw = cw;
-  p.stride = cw_stride;
-  p.sizes = d;
-  p.col_base = d + n;
-  p.nslices = static_cast<uint32_t>(n);
-  p.total_columns = h[2 * n];
-  p.pmask = xm + n;
-  p.rows = rows;
-  c->last_window_kernels |= ag::kDxVar;
-  if (ag::launch_var_decode(p, c->stream) != hipSuccess ||
-      ag::launch_var_strip(cw, cw_stride, d, n, strip, c->stream) != hipSuccess ||
-      ag::launch_pipe_store_masks(few, strip, d_present, 1, n, mask, -AG_RS_ERR_NOT_ENOUGH_SHARDS,
-                                  -AG_RS_ERR_INVALID_PADDING, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
   // no surplus and no slice with every data shred: every store mask is zero (pipe_coder_enqueue)
-  if (surplus || full_data) {
-    p.out_mask = mask;
-    c->last_encode_kernels |= ag::kEkVar;
-    if (ag::launch_var_encode(p, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  }
-  return pipe_coder_finish(c, n, out);  // synchronous
+  return pipe_coder_deshred_var(c, n, cw, cw_stride, d_present, d, d + n, h[2 * n], surplus || full_data, out);
 }
 
 }  // extern "C"
+
+namespace ag::host {
+// sizes | column prefix of a batch of mixed shred sizes (checked by the caller: each even, 2 ..
+// 1024) onto the device through the staging of ag_rs_coder_shred_batch_var's table (h_lens ->
+// d_lens, rewritten once its last upload has completed): for the composed var deshred, whose
+// kernels read the sizes from the first stage on, before any present words exist.  Valid on
+// the stream until the next coder shred call on the context.
+int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t** d_sizes, const uint32_t** d_col_base,
+                     uint32_t* total_columns) {
+  if (n > kVarMaxSlices) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (c->lens_ev) AG_HIP(hipEventSynchronize(c->lens_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->lens_ev, hipEventDisableTiming));
+  const size_t words = 2 * n + 1;
+  int st;
+  if ((st = c->h_lens.ensure(words * 4)) || (st = c->d_lens.ensure(words * 4, c->stream))) return st;
+  uint32_t* h = c->h_lens.as<uint32_t>();
+  var_column_table(S, n, h, h + n);
+  AG_HIP(hipMemcpyAsync(c->d_lens.ptr, h, words * 4, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->lens_ev, c->stream));
+  *d_sizes = c->d_lens.as<uint32_t>();
+  *d_col_base = *d_sizes + n;
+  *total_columns = h[2 * n];
+  return AG_RS_OK;
+}
+}  // namespace ag::host

@@ -379,9 +379,15 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
                         const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
                         uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes = nullptr,
                         size_t leaf_nodes_stride = 0, uint32_t leaves_per_tree = 0, size_t group_stride = 0,
-                        uint32_t skip_row = 0, bool roots_ready = false);
+                        uint32_t skip_row = 0, bool roots_ready = false, const uint32_t* leaf_sizes = nullptr,
+                        uint32_t size_group = 0);
 int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
                        int64_t* plen, size_t m, bool no_surplus = false);
+int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                           const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
+                           bool reencode, int64_t* plen);
+int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t** d_sizes, const uint32_t** d_col_base,
+                     uint32_t* total_columns);
 bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);
 
 }  // namespace host

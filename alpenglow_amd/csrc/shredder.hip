@@ -33,12 +33,20 @@ __device__ __forceinline__ bool plausible(const ShredColumns& c, const uint8_t* 
          c.data_len[t] == S && c.height[t] == kPipeHeight;
 }
 
-// one 64-lane wave per slice; lane j looks at shred j
-__global__ __launch_bounds__(64) void pipe_pick_kernel(const PipePickParams p) {
+// one 64-lane wave per slice; lane j looks at shred j.  VAR (p.slice_bytes set): the slice's own
+// shred size, and the picked rows gathered at a fixed stride of kPipeMaxShredBytes.
+template <bool VAR>
+__device__ __forceinline__ void pipe_pick_body(const PipePickParams& p) {
   const uint64_t s = blockIdx.x;
   const uint32_t j = threadIdx.x;
   const uint64_t t = s * kPipeShreds + j;
-  const bool fits = plausible(p.cols, p.wire_status, t, j, p.shred_bytes, p.num_data);
+  uint32_t S = p.shred_bytes;
+  uint64_t g_stride = p.shred_bytes;
+  if constexpr (VAR) {
+    S = __builtin_amdgcn_readfirstlane(p.slice_bytes[s]);
+    g_stride = kPipeMaxShredBytes;
+  }
+  const bool fits = plausible(p.cols, p.wire_status, t, j, S, p.num_data);
   p.plausible[t] = fits ? 1 : 0;
   const uint64_t ok = __builtin_amdgcn_ballot_w64(fits);
   const uint32_t pick = ok ? static_cast<uint32_t>(__builtin_ctzll(ok)) : kPipeNone;
@@ -47,8 +55,8 @@ __global__ __launch_bounds__(64) void pipe_pick_kernel(const PipePickParams p) {
   const uint64_t r = s * kPipeShreds + pick;
   // payload row (2-byte aligned: S is only even), proof, signature, header
   const uint16_t* src = reinterpret_cast<const uint16_t*>(p.cols.data + data_row_offset(p.cols, r));
-  uint16_t* dst = reinterpret_cast<uint16_t*>(p.g_data + s * p.shred_bytes);
-  for (uint32_t i = j; i < p.shred_bytes / 2; i += kPipeShreds) dst[i] = src[i];
+  uint16_t* dst = reinterpret_cast<uint16_t*>(p.g_data + s * g_stride);
+  for (uint32_t i = j; i < S / 2; i += kPipeShreds) dst[i] = src[i];
   const uint8_t* pp = p.cols.proof + r * p.cols.proof_stride;
   for (uint32_t i = j; i < 32 * kPipeHeight; i += kPipeShreds) p.g_proof[s * 32 * kPipeHeight + i] = pp[i];
   p.g_sig[64 * s + j] = p.cols.sig[64 * r + j];
@@ -59,6 +67,8 @@ __global__ __launch_bounds__(64) void pipe_pick_kernel(const PipePickParams p) {
     p.g_shred_index[s] = pick;
   }
 }
+__global__ __launch_bounds__(64) void pipe_pick_kernel(const PipePickParams p) { pipe_pick_body<false>(p); }
+__global__ __launch_bounds__(64) void pipe_pick_var_kernel(const PipePickParams p) { pipe_pick_body<true>(p); }
 
 __global__ __launch_bounds__(256) void pipe_cache_kernel(const uint8_t* pick, const uint8_t* pick_status,
                                                          uint64_t nslices, uint8_t* has_cached) {
@@ -67,11 +77,14 @@ __global__ __launch_bounds__(256) void pipe_cache_kernel(const uint8_t* pick, co
   has_cached[s] = pick[s] != kPipeNone && pick_status[s] == 0 ? 1 : 0;  // kShredOk
 }
 
-__global__ __launch_bounds__(64) void pipe_check_kernel(const PipeCheckParams p) {
+template <bool VAR>
+__device__ __forceinline__ void pipe_check_body(const PipeCheckParams& p) {
   const uint64_t s = blockIdx.x;
   const uint32_t j = threadIdx.x;
   const uint64_t t = s * kPipeShreds + j;
-  const bool valid = plausible(p.cols, p.wire_status, t, j, p.shred_bytes, p.num_data) && p.val_status[t] == 0;
+  uint32_t S = p.shred_bytes;
+  if constexpr (VAR) S = __builtin_amdgcn_readfirstlane(p.slice_bytes[s]);
+  const bool valid = plausible(p.cols, p.wire_status, t, j, S, p.num_data) && p.val_status[t] == 0;
   const uint64_t v = __builtin_amdgcn_ballot_w64(valid);
   if (v == 0) {
     if (j == 0) p.present[s] = 0;
@@ -97,6 +110,8 @@ __global__ __launch_bounds__(64) void pipe_check_kernel(const PipeCheckParams p)
   if (j < 32) p.root[32 * s + j] = p.roots[32 * r + j];
   p.sig[64 * s + j] = p.cols.sig[64 * r + j];
 }
+__global__ __launch_bounds__(64) void pipe_check_kernel(const PipeCheckParams p) { pipe_check_body<false>(p); }
+__global__ __launch_bounds__(64) void pipe_check_var_kernel(const PipeCheckParams p) { pipe_check_body<true>(p); }
 
 __global__ __launch_bounds__(256) void pipe_root_cmp_kernel(const uint8_t* a, const uint8_t* b, uint64_t nslices,
                                                             uint8_t* same) {
@@ -251,7 +266,8 @@ hipError_t launch_pipe_expand(const PipeExpandParams& p, hipStream_t stream) {
 hipError_t launch_pipe_pick(const PipePickParams& p, hipStream_t stream) {
   if (p.nslices == 0) return hipSuccess;
   if (p.nslices > 0x7FFFFFFFull || p.cols.proof_stride < 32 * kPipeHeight) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pipe_pick_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
+  if (p.slice_bytes) hipLaunchKernelGGL(pipe_pick_var_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
+  else hipLaunchKernelGGL(pipe_pick_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
   return hipGetLastError();
 }
 
@@ -266,7 +282,8 @@ hipError_t launch_pipe_cache_flags(const uint8_t* pick, const uint8_t* pick_stat
 hipError_t launch_pipe_check(const PipeCheckParams& p, hipStream_t stream) {
   if (p.nslices == 0) return hipSuccess;
   if (p.nslices > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pipe_check_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
+  if (p.slice_bytes) hipLaunchKernelGGL(pipe_check_var_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
+  else hipLaunchKernelGGL(pipe_check_kernel, dim3(static_cast<unsigned>(p.nslices)), dim3(64), 0, stream, p);
   return hipGetLastError();
 }
 

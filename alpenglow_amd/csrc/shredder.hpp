@@ -14,6 +14,7 @@ constexpr uint32_t kPipeShreds = 64;   // TOTAL_SHREDS (shredder.rs:47)
 constexpr uint32_t kPipeData = 32;     // DATA_SHREDS (shredder.rs:43)
 constexpr uint32_t kPipeHeight = 6;    // Merkle path length of a 64-leaf slice tree
 constexpr uint32_t kPipeNone = 0xFFu;  // no shred picked
+constexpr uint32_t kPipeMaxShredBytes = 1024;  // MAX_DATA_PER_SHRED: the row stride of picks of mixed sizes
 
 // Per-shred columns of the shred side / fill side: kind (data shreds first), shred_index,
 // data_len = S (or the slice's own size, slice_bytes) and height; rows whose skip bit is set get data_len = ~0 (the serializer then
@@ -53,6 +54,9 @@ struct PipePickParams {
   uint8_t* g_sig;               // [nslices][64]
   uint8_t* has_cached;          // [nslices]: filled by launch_pipe_cache_flags
   uint8_t* plausible;           // [nslices * 64] out: shred t parsed and fits its slot
+  // nullable: slice s's shred size instead of shred_bytes (device, [nslices]; the rows of cols
+  // packed at that size, cols.row_sizes); g_data is then [nslices][kPipeMaxShredBytes]
+  const uint32_t* slice_bytes;
 };
 hipError_t launch_pipe_pick(const PipePickParams& p, hipStream_t stream);
 // has_cached[s] = the picked shred of slice s passed its signature check.
@@ -77,6 +81,7 @@ struct PipeCheckParams {
   uint64_t* slice_index;
   uint8_t* is_last;
   uint8_t* sig;                // [nslices][64] out
+  const uint32_t* slice_bytes;  // nullable: slice s's shred size instead of shred_bytes (PipePickParams)
 };
 hipError_t launch_pipe_check(const PipeCheckParams& p, hipStream_t stream);
 

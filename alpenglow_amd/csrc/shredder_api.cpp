@@ -1,5 +1,5 @@
 // Host side of the composed shredders: ag_shredder_shred_batch[_var|_kind] and
-// ag_shredder_deshred_batch[_kind] (include/alpenglow_rs.h), the four shredders of shredder.rs
+// ag_shredder_deshred_batch[_var|_kind] (include/alpenglow_rs.h), the four shredders of shredder.rs
 // (Regular, CodingOnly, PETS, AONT) chained on the device from the batched stages of rs_api.cpp
 // (slice framing, ReedSolomonCoder, Merkle trees, signatures, all-or-nothing transforms; the
 // coder's encode / decode dispatch is rs_dispatch.cpp) and
@@ -290,10 +290,16 @@ struct DeshredViews {
 // (one signature per lane: a latency-bound kernel).  leaf_nodes (nullable; with its stride and
 // leaves_per_tree): that verify also keeps each shred's leaf digest there, at (slice, index),
 // for a Merkle rebuild's level 0.
-int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint8_t* packets,
-                  size_t packet_stride, const uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords,
-                  uint8_t* leaf_nodes, size_t leaf_nodes_stride, uint32_t leaves_per_tree, DeshredViews* v) {
+// d_sizes (device, nullable; Regular only): one shred size per slice, rows packed at the slice's
+// own size from k.group_stride (the slice stride; S is 0 then) -- every stage reads the slice's
+// size where it reads S: the parse (row capacity), the slot check of pick / check, the leaf size
+// of both verifies.  The picked rows are gathered at a fixed stride of 1024 bytes.
+int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint32_t* d_sizes,
+                  const uint8_t* packets, size_t packet_stride, const uint32_t* packet_lens, const uint8_t* pk,
+                  uint8_t* codewords, uint8_t* leaf_nodes, size_t leaf_nodes_stride, uint32_t leaves_per_tree,
+                  DeshredViews* v) {
   const size_t N = n * ag::kPipeShreds;
+  const size_t row = d_sizes ? size_t{AG_RS_MAX_DATA_PER_SHRED} : S;  // row capacity; stride of the picked rows
   int st;
   uint8_t *kind, *slot, *sidx, *last, *shidx, *dlen, *sig, *proof, *height, *wire, *vstat, *roots;
   if ((st = pipe_buf(c, kBufKind, N, &kind)) || (st = pipe_buf(c, kBufSlot, 8 * N, &slot)) ||
@@ -304,7 +310,7 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
       (st = pipe_buf(c, kBufValStatus, N, &vstat)) || (st = pipe_buf(c, kBufRoots, 32 * N, &roots)))
     return st;
   uint8_t *pick, *gdata, *gproof, *gslot, *gsidx, *glast, *gidx, *gsig, *pstat, *commits, *hasc;
-  if ((st = pipe_buf(c, kBufPick, n, &pick)) || (st = pipe_buf(c, kBufPickData, n * S, &gdata)) ||
+  if ((st = pipe_buf(c, kBufPick, n, &pick)) || (st = pipe_buf(c, kBufPickData, n * row, &gdata)) ||
       (st = pipe_buf(c, kBufPickProof, kPipeProofBytes * n, &gproof)) ||
       (st = pipe_buf(c, kBufPickSlot, 8 * n, &gslot)) || (st = pipe_buf(c, kBufPickSliceIndex, 8 * n, &gsidx)) ||
       (st = pipe_buf(c, kBufPickIsLast, n, &glast)) || (st = pipe_buf(c, kBufPickShredIndex, 4 * n, &gidx)) ||
@@ -325,9 +331,10 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   cols.is_last = last;
   cols.shred_index = reinterpret_cast<uint32_t*>(shidx);
   cols.data = codewords + k.row0 * S;
-  cols.data_stride = S;
+  cols.data_stride = row;
   cols.group_stride = k.group_stride;
   cols.skip_row = k.skip;
+  cols.row_sizes = d_sizes;
   cols.data_len = reinterpret_cast<uint32_t*>(dlen);
   cols.sig = sig;
   cols.proof = proof;
@@ -351,7 +358,8 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   pp.g_shred_index = reinterpret_cast<uint32_t*>(gidx);
   pp.g_sig = gsig;
   pp.plausible = plaus;  // per shred: the datagram parsed and fits its slot
-  AG_HIP(hipMemsetAsync(gdata, 0, n * S, c->stream));  // slices without a pick: defined bytes
+  pp.slice_bytes = d_sizes;
+  AG_HIP(hipMemsetAsync(gdata, 0, n * row, c->stream));  // slices without a pick: defined bytes
   AG_HIP(hipMemsetAsync(gidx, 0, 4 * n, c->stream));
   if (ag::launch_pipe_pick(pp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   ag::MerkleVerifyParams mp{};
@@ -371,18 +379,20 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   mp.leaves_per_tree = leaves_per_tree;
   mp.group_stride = k.group_stride;
   mp.skip_row = k.skip;
+  mp.leaf_sizes = d_sizes;  // (the full pass: one size per 64 rows, the leaf address follows the packed rows)
+  mp.size_group = d_sizes ? ag::kPipeShreds : 0;
   AG_HIP(hipEventRecord(c->side_fork, c->stream));
   if (hipStreamWaitEvent(c->side, c->side_fork, 0) != hipSuccess ||
       ag::launch_merkle_verify(mp, c->side) != hipSuccess || hipEventRecord(c->side_join, c->side) != hipSuccess)
     return drain_side(c, AG_RS_ERR_DEVICE);
-  if ((st = shred_validate_impl(c, n, gdata, S, S, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
+  if ((st = shred_validate_impl(c, n, gdata, row, row, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
                                 pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, nullptr, pstat,
-                                nullptr, commits)))
+                                nullptr, commits, nullptr, 0, 0, 0, 0, false, d_sizes, d_sizes ? 1 : 0)))
     return drain_side(c, st);
   if (ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream) != hipSuccess ||
       hipStreamWaitEvent(c->stream, c->side_join, 0) != hipSuccess)
     return drain_side(c, AG_RS_ERR_DEVICE);
-  if ((st = shred_validate_impl(c, N, cols.data, S, S, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
+  if ((st = shred_validate_impl(c, N, cols.data, row, row, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
                                 cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds, plaus,
                                 vstat, roots, nullptr, leaf_nodes, leaf_nodes_stride, leaves_per_tree, k.group_stride,
                                 k.skip, true)))
@@ -409,6 +419,7 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   kp.slice_index = reinterpret_cast<uint64_t*>(v->ssidx);
   kp.is_last = v->slast;
   kp.sig = v->ssig;
+  kp.slice_bytes = d_sizes;
   if (ag::launch_pipe_check(kp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   return read_pipe_meta(c, v->d_present, n, &v->h);
 }
@@ -441,7 +452,8 @@ void pipe_statuses(size_t n, const int64_t* plen, const uint8_t* h_same, const u
 // fill_missing_shreds: the datagrams of the absent slots of the slices with ok[s], serialized
 // into their packets; their lengths go to *fresh (pipe_merge_lens moves the final slices'
 // lengths into packet_lens), the uploaded flags to *d_ok.  Enqueued only: `ok` is host memory
-// the upload reads, so the caller synchronizes before it changes.
+// the upload reads, so the caller synchronizes before it changes.  Slices of mixed sizes
+// (v.cols.row_sizes, deshred_front's d_sizes): each datagram at its slice's own size.
 int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const DeshredViews& v, const uint8_t* ok,
                  uint8_t* packets, size_t packet_stride, uint8_t** d_ok, uint32_t** fresh) {
   const size_t N = n * ag::kPipeShreds;
@@ -460,6 +472,7 @@ int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const 
   ep.shred_index = v.cols.shred_index;
   ep.data_len = v.cols.data_len;
   ep.height = v.cols.height;
+  ep.slice_bytes = v.cols.row_sizes;
   if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   ag::ShredColumns fc = v.cols;
   fc.slot = v.d_slot;
@@ -477,14 +490,21 @@ int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const 
 // (present bit mask) go through ReedSolomonCoder::deshred with the crate's EXACT decoder,
 // and the Merkle rebuild (roots2 row s, the slice's proof rows), root comparison and
 // SlicePayload parse are redone for this slice.  Outputs replace slice s's entries.
-int pipe_rerun_exact(ag_rs_ctx* c, const ShredderKind& k, size_t s, size_t S, const uint8_t* packets,
-                     size_t packet_stride, const uint32_t* packet_lens, const DeshredViews& v, uint8_t* codewords,
-                     uint8_t* same, int64_t* plen, uint8_t* h_same, uint8_t* sstat, uint8_t* parent_flag,
-                     uint8_t* parent_id, uint32_t* data_offset, uint32_t* data_len) {
+// S: the slice's shred size; its 64 rows are packed at S from codewords + s * slice_stride (64 S
+// in the uniform call; with mixed sizes the rows are only 2-byte aligned, which the one-slice
+// uniform calls take: the byte copy of the parse, the byte-aligned leaf kernel).
+int pipe_rerun_exact(ag_rs_ctx* c, const ShredderKind& k, size_t s, size_t S, size_t slice_stride,
+                     const uint8_t* packets, size_t packet_stride, const uint32_t* packet_lens,
+                     const DeshredViews& v, uint8_t* codewords, uint8_t* same, int64_t* plen, uint8_t* h_same,
+                     uint8_t* sstat, uint8_t* parent_flag, uint8_t* parent_id, uint32_t* data_offset,
+                     uint32_t* data_len) {
   constexpr size_t kRows = ag::kPipeShreds;
   const size_t r0 = s * kRows, cw_stride = kRows * S;
-  uint8_t* cw = codewords + s * cw_stride;
+  uint8_t* cw = codewords + s * slice_stride;
   ag::ShredColumns rc = v.cols;
+  rc.data_stride = S;  // one slice, its rows at t * S
+  rc.group_stride = 0;
+  rc.row_sizes = nullptr;
   rc.kind += r0;
   rc.slot += r0;
   rc.slice_index += r0;
@@ -512,6 +532,148 @@ int pipe_rerun_exact(ag_rs_ctx* c, const ShredderKind& k, size_t s, size_t S, co
   AG_HIP(hipMemcpyAsync(h_same, same + s, 1, hipMemcpyDeviceToHost, c->stream));
   // synchronous: h_same has landed when it returns
   return ag_slice_parse_batch(c, 1, cw, cw_stride, plen, sstat, parent_flag, parent_id, data_offset, data_len);
+}
+
+// RegularShredder's deshred, the body of ag_shredder_deshred_batch (sizes null: every shred S
+// bytes, cw_stride = 64 S) and of ag_shredder_deshred_batch_var (sizes: HOST, one checked shred
+// size per slice, S = 0; slice s's rows packed at sizes[s] from codewords + s * cw_stride).  The
+// sizes go up once (upload_var_sizes) and every kernel reads them from the device; the stages
+// and their order are the same, so the number of launches does not depend on the mix.
+int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uint8_t* packets, size_t packet_stride,
+                    uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords, size_t cw_stride, int32_t* status,
+                    uint64_t* slots_out, uint64_t* slice_indices_out, uint8_t* is_last_out,
+                    uint8_t* parent_flags_out, uint8_t* parent_ids_out, uint32_t* data_offsets_out,
+                    uint32_t* data_lens_out) {
+  const size_t N = n * ag::kPipeShreds;
+  int st;
+  ShredderKind k;
+  shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
+  const uint32_t *d_sizes = nullptr, *d_col_base = nullptr;
+  uint32_t total_columns = 0;
+  if (sizes) {
+    if ((st = upload_var_sizes(c, n, sizes, &d_sizes, &d_col_base, &total_columns))) return st;
+    k.group_stride = cw_stride;  // rows packed at each slice's own size: addressed per slice
+  }
+  // 1-3. the kept shreds of every slice (payload rows straight into the codewords: row 64 s + j
+  //      is shard j of slice s), with every plausible shred's leaf digest kept for the Merkle
+  //      rebuild's level 0: step 5 hashes only the rows the coder restores or may rewrite
+  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
+  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream))) return st;
+  uint8_t* nodes = c->d_merkle_nodes.as<uint8_t>();
+  DeshredViews v;
+  if ((st = deshred_front(c, k, n, S, d_sizes, packets, packet_stride, packet_lens, pk, codewords, nodes, nodes_stride,
+                          ag::kPipeShreds, &v)))
+    return st;
+  const uint64_t* h_present = v.h.present;
+  // 4. ReedSolomonCoder::deshred over the kept shreds (restores the data shreds, re-encodes
+  //    all coding shreds, strips the padding); on the device for whole-chunk shreds
+  std::vector<int64_t> plen(n);
+  bool no_reencode = true;  // no surplus shreds and no slice with every data shred
+  for (size_t s = 0; s < n && no_reencode; ++s)
+    no_reencode = __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData) &&
+                  (h_present[s] & 0xFFFFFFFFull) != 0xFFFFFFFFull;
+  const bool device_coder = sizes || pipe_tail_ok(S, kDataShreds, no_reencode);
+  if (sizes) {
+    // the var coder's device stages (every even size; exactly-32 slices get their absent coding
+    // shreds from the decode, surplus slices the re-encode under their store masks)
+    c->last_encode_kernels = 0;
+    c->last_window_kernels = 0;
+    if ((st = pipe_coder_deshred_var(c, n, codewords, cw_stride, v.d_present, d_sizes, d_col_base, total_columns,
+                                     !no_reencode, plen.data())))
+      return st;
+  } else if (device_coder) {
+    if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, v.d_present, plen.data(), kDataShreds, no_reencode)))
+      return st;
+  } else {
+    std::vector<uint8_t> dp(n * ag::kPipeData), cp(n * k.m);
+    for (size_t s = 0; s < n; ++s) coder_flags(k, h_present[s], &dp[s * ag::kPipeData], &cp[s * k.m]);
+    if ((st = ag_rs_coder_deshred_batch(c, k.m, n, S, codewords, cw_stride, dp.data(), cp.data(), AG_RS_DECODE_ANY_K,
+                                        plen.data())))
+      return st;
+  }
+  // 5. check_merkle_tree: the rebuilt tree's root must be the signed one; its paths serve
+  //    the reconstructed datagrams.  Kept shreds the coder left as received reuse the digests
+  //    their proof check computed (same bytes); restored rows, and coding rows the re-encode
+  //    may have rewritten, are hashed again.
+  //    Mixed sizes: the same, verbatim -- the var verify wrote the kept rows' digests from the
+  //    same packed bytes the var leaf kernel would read, the var coder stage obeys the same store
+  //    masks, and only the flagged leaves are hashed again.
+  //    Invariant the reuse depends on (ADVICE r5): present ⊆ active ∧ proof-ok.  Every kept
+  //    shred (a bit of d_present, set by pipe_check only for shreds that were active in the
+  //    step-3 verify and whose derived root matched) had its leaf digest written to
+  //    d_merkle_nodes at (slice, index) by that verify; nothing between step 3 and here writes
+  //    those rows of the codeword or those nodes (the coder stage touches only absent rows
+  //    and, per the store masks, coding rows the leaf flags mark for re-hashing).  The verify
+  //    also stores digests of rows it then rejects: those rows are not in d_present, so the
+  //    flags below re-hash or ignore them.  A new step in between that writes kept rows or
+  //    d_merkle_nodes must clear the matching present bits or re-hash.
+  {
+    uint8_t *lflags, *llist;
+    if ((st = pipe_buf(c, kBufLeafFlags, N, &lflags)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &llist)) ||
+        (st = ensure_empty_roots(c)))
+      return st;
+    // the host coder path (shreds not whole 64-byte chunks) re-encodes every coding shred; the
+    // var coder never does: its decode restores the absent coding shreds of exactly-32 slices,
+    // and the kernel flags the surplus slices' coding rows itself
+    if (ag::launch_pipe_leaf_flags(v.d_present, n, !device_coder, lflags, c->stream) != hipSuccess)
+      return AG_RS_ERR_DEVICE;
+    ag::MerkleBuildParams mb{};
+    mb.leaves = codewords;
+    mb.leaf_stride = S;
+    mb.slice_stride = cw_stride;
+    mb.leaf_bytes = static_cast<uint32_t>(S);
+    mb.n_leaves = ag::kPipeShreds;
+    mb.nslices = n;
+    mb.empty_roots = c->d_empty_roots.as<uint32_t>();
+    mb.roots = v.roots2;
+    mb.proofs = v.cols.proof;
+    mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
+    mb.hash_leaf = lflags;
+    mb.list = reinterpret_cast<uint32_t*>(llist);
+    mb.leaf_sizes = d_sizes;  // (leaf_stride / leaf_bytes unused then: rows at the slice's own size)
+    c->last_merkle_kernels = 0;
+    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
+      return AG_RS_ERR_DEVICE;
+  }
+  uint8_t* same;
+  if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
+  if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  std::vector<uint8_t> h_same(n);
+  AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
+  // 6. SlicePayload::try_from
+  std::vector<uint8_t> sstat(n);
+  if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
+                                 parent_ids_out, data_offsets_out, data_lens_out)))
+    return st;  // synchronous: h_same has landed
+  // 6b. The crate's decoder reads every kept shred (reed_solomon.rs:154-166); the pass above
+  //     reads 32 of them (ANY_K).  On a consistent slice both restore the same bytes (MDS), and
+  //     a slice that passed check_merkle_tree is consistent: the rebuilt codeword matches the
+  //     signed root that commits every kept shred.  A slice that failed the padding or the
+  //     Merkle check with more than 32 kept shreds may hold an inconsistent shred the ANY_K
+  //     pass did not read (a leader signing a non-codeword), and the crate's bytes -- hence
+  //     the error, BadEncoding vs InvalidMerkleTree -- can differ.  Such slices are decoded
+  //     again from their received bytes with EXACT and re-checked, one by one (honest
+  //     leaders never produce them).
+  for (size_t s = 0; s < n; ++s) {
+    const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
+    if (!failed || __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData)) continue;
+    if ((st = pipe_rerun_exact(c, k, s, sizes ? sizes[s] : S, cw_stride, packets, packet_stride, packet_lens, v, codewords, same, &plen[s],
+                               &h_same[s], &sstat[s], parent_flags_out + s,
+                               parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s, data_offsets_out + s,
+                               data_lens_out + s)))
+      return st;
+  }
+  std::vector<uint8_t> ok(n);
+  pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
+                is_last_out);
+  // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
+  uint8_t* d_ok;
+  uint32_t* fresh;
+  if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
+    return AG_RS_ERR_DEVICE;
+  AG_HIP(hipStreamSynchronize(c->stream));  // host vectors read by async copies
+  return AG_RS_OK;
 }
 
 }  // namespace
@@ -619,116 +781,38 @@ int ag_shredder_deshred_batch(ag_rs_ctx* c, size_t nslices, size_t S, uint8_t* p
     return AG_RS_ERR_INVALID_ARGUMENT;
   if (nslices == 0) return AG_RS_OK;
   if (c->enter()) return AG_RS_ERR_DEVICE;
-  const size_t n = nslices, N = n * ag::kPipeShreds, cw_stride = ag::kPipeShreds * S;
-  int st;
-  ShredderKind k;
-  shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
-  // 1-3. the kept shreds of every slice (payload rows straight into the codewords: row 64 s + j
-  //      is shard j of slice s), with every plausible shred's leaf digest kept for the Merkle
-  //      rebuild's level 0: step 5 hashes only the rows the coder restores or may rewrite
-  const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
-  if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream))) return st;
-  uint8_t* nodes = c->d_merkle_nodes.as<uint8_t>();
-  DeshredViews v;
-  if ((st = deshred_front(c, k, n, S, packets, packet_stride, packet_lens, pk, codewords, nodes, nodes_stride,
-                          ag::kPipeShreds, &v)))
-    return st;
-  const uint64_t* h_present = v.h.present;
-  // 4. ReedSolomonCoder::deshred over the kept shreds (restores the data shreds, re-encodes
-  //    all coding shreds, strips the padding); on the device for whole-chunk shreds
-  std::vector<int64_t> plen(n);
-  bool no_reencode = true;  // no surplus shreds and no slice with every data shred
-  for (size_t s = 0; s < n && no_reencode; ++s)
-    no_reencode = __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData) &&
-                  (h_present[s] & 0xFFFFFFFFull) != 0xFFFFFFFFull;
-  const bool device_coder = pipe_tail_ok(S, kDataShreds, no_reencode);
-  if (device_coder) {
-    if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, v.d_present, plen.data(), kDataShreds, no_reencode)))
-      return st;
-  } else {
-    std::vector<uint8_t> dp(n * ag::kPipeData), cp(n * k.m);
-    for (size_t s = 0; s < n; ++s) coder_flags(k, h_present[s], &dp[s * ag::kPipeData], &cp[s * k.m]);
-    if ((st = ag_rs_coder_deshred_batch(c, k.m, n, S, codewords, cw_stride, dp.data(), cp.data(), AG_RS_DECODE_ANY_K,
-                                        plen.data())))
-      return st;
+  return regular_deshred(c, nslices, S, nullptr, packets, packet_stride, packet_lens, pk, codewords,
+                         ag::kPipeShreds * S, status, slots_out, slice_indices_out, is_last_out, parent_flags_out,
+                         parent_ids_out, data_offsets_out, data_lens_out);
+}
+
+// Shredder::deshred over slices of mixed shred sizes (the layout of ag_shredder_shred_batch_var):
+// every check on the host before the first launch, then regular_deshred with the size table.
+int ag_shredder_deshred_batch_var(ag_rs_ctx* c, size_t nslices, const uint32_t* shred_bytes, uint8_t* packets,
+                                  size_t packet_stride, uint32_t* packet_lens, const uint8_t* pk, uint8_t* codewords,
+                                  size_t codeword_stride, int32_t* status, uint64_t* slots_out,
+                                  uint64_t* slice_indices_out, uint8_t* is_last_out, uint8_t* parent_flags_out,
+                                  uint8_t* parent_ids_out, uint32_t* data_offsets_out, uint32_t* data_lens_out) {
+  if (!c || nslices >= (size_t{1} << 24)) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (!shred_bytes || !packets || !packet_lens || !pk || !codewords || !status || !slots_out || !slice_indices_out ||
+      !is_last_out || !parent_flags_out || !parent_ids_out || !data_offsets_out || !data_lens_out ||
+      reinterpret_cast<uintptr_t>(codewords) % 16 || codeword_stride % 16)
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  size_t max_s = 0, need = 0;
+  for (size_t s = 0; s < nslices; ++s) {
+    if (shred_bytes[s] == 0 || shred_bytes[s] % 2 || shred_bytes[s] > AG_RS_MAX_DATA_PER_SHRED)
+      return AG_RS_ERR_INVALID_ARGUMENT;
+    max_s = std::max<size_t>(max_s, shred_bytes[s]);
   }
-  // 5. check_merkle_tree: the rebuilt tree's root must be the signed one; its paths serve
-  //    the reconstructed datagrams.  Kept shreds the coder left as received reuse the digests
-  //    their proof check computed (same bytes); restored rows, and coding rows the re-encode
-  //    may have rewritten, are hashed again.
-  //    Invariant the reuse depends on (ADVICE r5): present ⊆ active ∧ proof-ok.  Every kept
-  //    shred (a bit of d_present, set by pipe_check only for shreds that were active in the
-  //    step-3 verify and whose derived root matched) had its leaf digest written to
-  //    d_merkle_nodes at (slice, index) by that verify; nothing between step 3 and here writes
-  //    those rows of the codeword or those nodes (the coder stage touches only absent rows
-  //    and, per the store masks, coding rows the leaf flags mark for re-hashing).  The verify
-  //    also stores digests of rows it then rejects: those rows are not in d_present, so the
-  //    flags below re-hash or ignore them.  A new step in between that writes kept rows or
-  //    d_merkle_nodes must clear the matching present bits or re-hash.
-  {
-    uint8_t *lflags, *llist;
-    if ((st = pipe_buf(c, kBufLeafFlags, N, &lflags)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &llist)) ||
-        (st = ensure_empty_roots(c)))
-      return st;
-    // the host coder path (shreds not whole 64-byte chunks) re-encodes every coding shred
-    if (ag::launch_pipe_leaf_flags(v.d_present, n, !device_coder, lflags, c->stream) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-    ag::MerkleBuildParams mb{};
-    mb.leaves = codewords;
-    mb.leaf_stride = S;
-    mb.slice_stride = cw_stride;
-    mb.leaf_bytes = static_cast<uint32_t>(S);
-    mb.n_leaves = ag::kPipeShreds;
-    mb.nslices = n;
-    mb.empty_roots = c->d_empty_roots.as<uint32_t>();
-    mb.roots = v.roots2;
-    mb.proofs = v.cols.proof;
-    mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
-    mb.hash_leaf = lflags;
-    mb.list = reinterpret_cast<uint32_t*>(llist);
-    c->last_merkle_kernels = 0;
-    if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
-      return AG_RS_ERR_DEVICE;
-  }
-  uint8_t* same;
-  if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
-  if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  std::vector<uint8_t> h_same(n);
-  AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
-  // 6. SlicePayload::try_from
-  std::vector<uint8_t> sstat(n);
-  if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
-                                 parent_ids_out, data_offsets_out, data_lens_out)))
-    return st;  // synchronous: h_same has landed
-  // 6b. The crate's decoder reads every kept shred (reed_solomon.rs:154-166); the pass above
-  //     reads 32 of them (ANY_K).  On a consistent slice both restore the same bytes (MDS), and
-  //     a slice that passed check_merkle_tree is consistent: the rebuilt codeword matches the
-  //     signed root that commits every kept shred.  A slice that failed the padding or the
-  //     Merkle check with more than 32 kept shreds may hold an inconsistent shred the ANY_K
-  //     pass did not read (a leader signing a non-codeword), and the crate's bytes -- hence
-  //     the error, BadEncoding vs InvalidMerkleTree -- can differ.  Such slices are decoded
-  //     again from their received bytes with EXACT and re-checked, one by one (honest
-  //     leaders never produce them).
-  for (size_t s = 0; s < n; ++s) {
-    const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
-    if (!failed || __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData)) continue;
-    if ((st = pipe_rerun_exact(c, k, s, S, packets, packet_stride, packet_lens, v, codewords, same, &plen[s],
-                               &h_same[s], &sstat[s], parent_flags_out + s,
-                               parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s, data_offsets_out + s,
-                               data_lens_out + s)))
-      return st;
-  }
-  std::vector<uint8_t> ok(n);
-  pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
-                is_last_out);
-  // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
-  uint8_t* d_ok;
-  uint32_t* fresh;
-  if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
-  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  AG_HIP(hipStreamSynchronize(c->stream));  // host vectors read by async copies
-  return AG_RS_OK;
+  // the kernels' bounds: no row past its slice's stride, no datagram past its slot
+  if (codeword_stride < ag::kPipeShreds * max_s || ag_shred_datagram_bytes(max_s, ag::kPipeHeight, &need) ||
+      packet_stride < need)
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  return regular_deshred(c, nslices, 0, shred_bytes, packets, packet_stride, packet_lens, pk, codewords,
+                         codeword_stride, status, slots_out, slice_indices_out, is_last_out, parent_flags_out,
+                         parent_ids_out, data_offsets_out, data_lens_out);
 }
 
 // ---- the other three shredders of shredder.rs composed (CodingOnly, PETS, AONT) -------------
@@ -812,7 +896,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   auto run_pass = [&](int pass, bool* redo) -> int {
     // 1-3. the kept shreds of every slice (the Regular pipeline's steps with this shredder's data
     //      / coding layout), payloads parsed straight into their codeword rows
-    if ((st = deshred_front(c, k, n, S, packets, packet_stride, packet_lens, pk, codewords, nullptr, 0, 0, &v)))
+    if ((st = deshred_front(c, k, n, S, nullptr, packets, packet_stride, packet_lens, pk, codewords, nullptr, 0, 0, &v)))
       return st;
     const uint64_t* h_present = v.h.present;
     // 4. deshred_validated_shreds: ReedSolomonCoder::deshred over the kept shreds (in their

@@ -85,6 +85,13 @@ __device__ __forceinline__ bool word_rows(const ShredColumns& c) {
   return ((reinterpret_cast<uintptr_t>(c.data) | c.data_stride | c.group_stride) & 3) == 0;
 }
 
+// VAR (c.row_sizes set): the slice's own row size stands where data_stride does -- the expected
+// data length of the speculation and the capacity of the row.  One wave handles one datagram, so
+// the size is wave-uniform.  Row j of slice g sits at g * group_stride + j * size, packed: a
+// datagram longer than the size would run into the next row (perhaps a kept shred) or past the
+// slice's 64 * size bytes, so it is kWireTooLarge and never copied.  Rows are only 2-byte
+// aligned: the copy is copy16_any (no word path).
+template <bool VAR>
 __global__ __launch_bounds__(256) void shred_deserialize_kernel(const uint8_t* __restrict__ packets,
                                                                 uint64_t packet_stride,
                                                                 const uint32_t* __restrict__ packet_lens, uint64_t n,
@@ -93,12 +100,14 @@ __global__ __launch_bounds__(256) void shred_deserialize_kernel(const uint8_t* _
   const int lane = threadIdx.x & 63;
   if (t >= n) return;
   const uint8_t* pk = packets + t * packet_stride;
+  uint32_t row_size = 0;  // VAR: capacity of this datagram's data row
+  if constexpr (VAR) row_size = __builtin_amdgcn_readfirstlane(c.row_sizes[t / kTotalShreds]);
   // Speculation: a call's datagrams carry data_stride data bytes and a full-capacity proof (the
   // composed deshreds' rows: S bytes, 6 digests).  Their data, signature, proof length and proof
   // are loaded now, in the same round trip as the length and the header, where that layout fits
   // the packet row; the copy below uses them only if the parsed header matches (otherwise the
   // dependent loads run as before).  Every speculative access stays inside the packet row.
-  const uint32_t E = static_cast<uint32_t>(c.data_stride);
+  const uint32_t E = VAR ? row_size : static_cast<uint32_t>(c.data_stride);
   const uint32_t e_sig = kShredHeadBytes + E;
   const bool spec = E <= 1024 && c.proof_stride <= 256 && c.proof_stride % 16 == 0 &&
                     uint64_t{e_sig} + 72 + c.proof_stride <= packet_stride;
@@ -136,7 +145,7 @@ __global__ __launch_bounds__(256) void shred_deserialize_kernel(const uint8_t* _
     // bound plen before any multiply: 32 * plen wraps in u64 for plen >= 2^59
     if (plen > kMtuBytes / 32 || o_sig + 72 + 32 * plen != len) st = kWireMalformed;  // exact consumption
   }
-  if (st == kWireOk && (dlen > c.data_stride || 32 * plen > c.proof_stride)) st = kWireTooLarge;
+  if (st == kWireOk && (dlen > (VAR ? uint64_t{row_size} : c.data_stride) || 32 * plen > c.proof_stride)) st = kWireTooLarge;
   if (lane == 0) {
     status[t] = static_cast<uint8_t>(st);
     if (st == kWireOk) {
@@ -165,8 +174,12 @@ __global__ __launch_bounds__(256) void shred_deserialize_kernel(const uint8_t* _
     else if (16u * (lane - 4) < c.proof_stride) st16u(pp + 16 * (lane - 4), s_tail);
     return;
   }
-  if (word_rows(c)) copy_to_aligned(dd, pk + kShredHeadBytes, static_cast<uint32_t>(dlen), lane);
-  else for (uint32_t i = lane; i < dlen; i += 64) dd[i] = pk[kShredHeadBytes + i];
+  if constexpr (VAR) {
+    copy16_any(dd, pk + kShredHeadBytes, static_cast<uint32_t>(dlen), lane);
+  } else {
+    if (word_rows(c)) copy_to_aligned(dd, pk + kShredHeadBytes, static_cast<uint32_t>(dlen), lane);
+    else for (uint32_t i = lane; i < dlen; i += 64) dd[i] = pk[kShredHeadBytes + i];
+  }
   c.sig[64 * t + lane] = pk[o_sig + lane];
   for (uint32_t i = lane; i < 32 * plen; i += 64) pp[i] = pk[o_sig + 72 + i];
 }
@@ -178,8 +191,10 @@ __global__ __launch_bounds__(256) void shred_serialize_kernel(const ShredColumns
   const int lane = threadIdx.x & 63;
   if (t >= n) return;
   uint8_t* pk = packets + t * packet_stride;
-  // (row_sizes: one size per slice, wave-uniform like every other value here)
-  const uint32_t dlen = c.row_sizes ? c.row_sizes[t / kTotalShreds] : c.data_len[t], plen = c.height[t];
+  // (row_sizes: one size per slice, wave-uniform like every other value here; a row whose data_len
+  // is ~0 is skipped there too: the fill side's kept datagrams)
+  const uint32_t dl = c.data_len[t];
+  const uint32_t dlen = c.row_sizes && dl != 0xFFFFFFFFu ? c.row_sizes[t / kTotalShreds] : dl, plen = c.height[t];
   const uint32_t o_sig = kShredHeadBytes + dlen;
   if (dlen > c.data_stride || 32ull * plen > c.proof_stride || uint64_t{o_sig} + 72 + 32ull * plen > packet_stride) {
     if (lane == 0) packet_lens[t] = 0;  // does not fit the caller's rows: nothing written
@@ -226,8 +241,15 @@ hipError_t launch_shred_deserialize(const uint8_t* packets, uint64_t packet_stri
                                     uint64_t n, const ShredColumns& c, uint8_t* status, hipStream_t stream) {
   if (n == 0) return hipSuccess;
   if ((n + 3) / 4 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(shred_deserialize_kernel, dim3(static_cast<unsigned>((n + 3) / 4)), dim3(256), 0, stream,
-                     packets, packet_stride, packet_lens, n, c, status);
+  const dim3 grid(static_cast<unsigned>((n + 3) / 4));
+  if (c.row_sizes) {  // whole slices of 64 rows, sizes the row capacity bounds
+    if (n % kTotalShreds || !c.group_stride || c.data_stride > 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shred_deserialize_kernel<true>, grid, dim3(256), 0, stream, packets, packet_stride, packet_lens,
+                       n, c, status);
+  } else {
+    hipLaunchKernelGGL(shred_deserialize_kernel<false>, grid, dim3(256), 0, stream, packets, packet_stride, packet_lens, n,
+                       c, status);
+  }
   return hipGetLastError();
 }
 

@@ -33,11 +33,13 @@ struct ShredColumns {
   uint64_t group_stride;  // data row t at data + grouped_row_offset(t, data_stride, group_stride,
   uint32_t skip_row;      // skip_row) (group_stride 0: t * data_stride)
   uint32_t skip_sig;      // serialize only: leave the 64 signature bytes for launch_shred_sig_patch
-  // serialize only, nullable: one row size per slice (device, [n / 64]; slices of mixed shred
-  // sizes).  Row j of slice g = t / 64 then sits at data + g * group_stride + j * row_sizes[g]
-  // (packed at the slice's own size; skip_row unused) and the shred's data length is
-  // row_sizes[g] (data_len is not read; data_stride only bounds the size).  Null: the layout
-  // above, unchanged.
+  // nullable: one row size per slice (device, [n / 64]; slices of mixed shred sizes, each even
+  // and <= data_stride <= 1024, 64 * size <= group_stride -- the caller checks them on the
+  // host).  Row j of slice g = t / 64 then sits at data + g * group_stride + j * row_sizes[g]
+  // (packed at the slice's own size; skip_row unused).  Serialize: the shred's data length is
+  // row_sizes[g] (data_len only marks skipped rows, ~0; data_stride only bounds the size).
+  // Deserialize: row_sizes[g] is the row's capacity (a longer datagram is kWireTooLarge and not
+  // copied: it would overwrite the next row).  Null: the layout above, unchanged.
   const uint32_t* row_sizes;
 };
 __host__ __device__ inline uint64_t data_row_offset(const ShredColumns& c, uint64_t t) {

@@ -85,7 +85,7 @@ EXPORTS = (
     "ag_slice_sign_batch", "ag_shred_deserialize_batch", "ag_shred_serialize_batch", "ag_shred_datagram_bytes",
     "ag_slice_frame_batch", "ag_slice_parse_batch",
     "ag_shredder_shred_batch", "ag_shredder_deshred_batch", "ag_shredder_shred_batch_var",
-    "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind",
+    "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind", "ag_shredder_deshred_batch_var",
 )
 
 
@@ -180,6 +180,7 @@ def load():
         "ag_shredder_shred_batch_var": ([p, sz, p, p, p, sz, p, p, p, p, p, p, p, sz, p, p, p, p, sz, p, sz, p, p], i),
         "ag_shredder_shred_batch_kind": ([p, i, sz, sz, p, p, p, sz, p, p, p, p, p, p, p, p, sz, p, p, p, sz, p], i),
         "ag_shredder_deshred_batch_kind": ([p, i, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
+        "ag_shredder_deshred_batch_var": ([p, sz, p, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
     }
     sigs["ag_rs_internal_last_decode_classes"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_encode_kernels"] = ([p, p], i)  # test aid, not in the header
@@ -751,13 +752,14 @@ def merkle_build_batch_var(ctx: Context, nslices: int, leaf_bytes, leaves, slice
            "ag_merkle_build_batch_var")
 
 
-MERKLE_KERNELS = ("leaf_aligned", "leaf_byte", "leaf_var")
+MERKLE_KERNELS = ("leaf_aligned", "leaf_byte", "leaf_var", "leaf_var_flagged")
 
 
 def last_merkle_kernels(ctx: Context) -> set:
     """The leaf-kernel classes the last Merkle build on ``ctx`` launched (test aid; the bits of
     ``ag::MerkleLeafKernelBit``, merkle.hpp): uniform size with 16-byte-aligned rows, uniform size
-    through the byte loader, or one size per slice."""
+    through the byte loader, one size per slice, or one size per slice over the flagged leaves
+    only (a deshred's rebuild)."""
     out = ctypes.c_uint32(0)
     _check(load().ag_rs_internal_last_merkle_kernels(ctx.handle, ctypes.byref(out)), "last_merkle_kernels")
     return {name for i, name in enumerate(MERKLE_KERNELS) if out.value >> i & 1}
@@ -1101,6 +1103,33 @@ def shredder_deshred_batch(ctx: Context, nslices: int, shred_bytes: int, packets
                                             slots.ctypes.data, sidx.ctypes.data, last.ctypes.data, flags.ctypes.data,
                                             ids.ctypes.data, offs.ctypes.data, dl.ctypes.data),
            "ag_shredder_deshred_batch")
+    parents = _parent_list(flags, ids)
+    return DeshredBatch(st, slots, sidx, last, parents, offs, dl)
+
+
+def shredder_deshred_batch_var(ctx: Context, nslices: int, shred_bytes, packets, packet_stride: int, packet_lens,
+                               pk, codewords, codeword_stride: int) -> DeshredBatch:
+    """``shredder_deshred_batch`` over slices that each have their own shred size, in the layout
+    of ``shredder_shred_batch_var``: shred_bytes (host, one even size per slice; a follower takes
+    it from any stored datagram of the slice, its length - shred_datagram_bytes(0, 6)), slice s's
+    64 raw shreds packed at that size at codewords + s * codeword_stride, its datagrams in the
+    slots 64 s + j.  A datagram of another size counts as absent.  One call, whatever the mix."""
+    import numpy as np
+
+    sizes = _u32(shred_bytes, nslices)
+    st = np.zeros(nslices, np.int32)
+    slots = np.zeros(nslices, np.uint64)
+    sidx = np.zeros(nslices, np.uint64)
+    last = np.zeros(nslices, np.uint8)
+    flags = np.zeros(nslices, np.uint8)
+    ids = np.zeros((nslices, BLOCK_ID_BYTES), np.uint8)
+    offs = np.zeros(nslices, np.uint32)
+    dl = np.zeros(nslices, np.uint32)
+    _check(load().ag_shredder_deshred_batch_var(ctx.handle, nslices, sizes.ctypes.data, _optr(packets), packet_stride,
+                                                _optr(packet_lens), _optr(pk), _optr(codewords), codeword_stride,
+                                                st.ctypes.data, slots.ctypes.data, sidx.ctypes.data, last.ctypes.data,
+                                                flags.ctypes.data, ids.ctypes.data, offs.ctypes.data,
+                                                dl.ctypes.data), "ag_shredder_deshred_batch_var")
     parents = _parent_list(flags, ids)
     return DeshredBatch(st, slots, sidx, last, parents, offs, dl)
 

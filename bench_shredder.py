@@ -15,8 +15,9 @@ around each (synchronous) call.  Prints one JSON line; the verify block checks t
 trip (every payload and datagram restored) and a spot check against the CPU composition of
 the reference (oracle/shredder_oracle.py, checker only).
 
---mixed-sizes times the shred side over a block's mix of shred sizes (bench_coder.mixed_sizes)
-through ag_shredder_shred_batch_var against loops of the uniform call; see mixed_leg.
+--mixed-sizes times both sides over a block's mix of shred sizes (bench_coder.mixed_sizes):
+ag_shredder_shred_batch_var and ag_shredder_deshred_batch_var against loops of the uniform
+calls; see mixed_leg and mixed_deshred_leg.
 """
 from __future__ import annotations
 
@@ -47,7 +48,8 @@ def mixed_leg(args):
                      what a caller can do without the var call (host-bound: timed once)
     Per leg the median over --steps of the host's wall time from the call to the end of a
     synchronise.  One JSON line; the verify block compares var_mix's datagrams, lengths and roots
-    with runs_mix's."""
+    with runs_mix's.  The deshred side of the same block follows (mixed_deshred_leg), under the
+    line's "deshred" key."""
     import statistics
 
     import numpy as np
@@ -124,6 +126,9 @@ def mixed_leg(args):
     times["runs_mix"] = [t_runs]
     out = {k: {"wall_ms": statistics.median(v), "slices_per_s": n / (statistics.median(v) * 1e-3), "steps": len(v)}
            for k, v in times.items()}
+    var()  # the block's datagrams again (the uniform leg ran last)
+    deshred = mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pkts, lens, timed,
+                                lambda: uniform(1024, d1024))
     print(json.dumps({
         "metric": "slices/s composed RegularShredder shred over a block's mix of shred sizes, one var call",
         "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "higher_is_better": True, "n_gpus": 1,
@@ -135,8 +140,103 @@ def mixed_leg(args):
                    "var_mix_over_presorted_mix": out["presorted_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
                    "var_mix_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_mix"]["wall_ms"]},
         "verify": {"var_mix_equals_runs_mix": same},
+        "deshred": deshred,
     }), flush=True)
     ctx.close()
+
+
+def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pkts, lens, timed, shred_1024):
+    """The follower's side of --mixed-sizes: the block mixed_leg shredded (pkts / lens hold
+    ag_shredder_shred_batch_var's datagrams), a random 32 of 64 datagrams per slice received,
+    legs interleaved step by step:
+      var_mix        ag_shredder_deshred_batch_var, one call
+      presorted_mix  the datagrams already regrouped by size, ag_shredder_deshred_batch once per
+                     distinct size (the regrouping is not timed)
+      runs_mix       the same with the regrouping copy timed: what a caller does without the var
+                     call (the deshred fills datagram slots in place, so slices of one size have
+                     to sit together)
+      uniform_1024   ag_shredder_deshred_batch on maximum slices
+    Before each timed call only the lengths are reset (absent slots: length 0).  verify: every
+    slice of every leg has status OK, and var_mix's payloads equal the input."""
+    import statistics
+
+    import numpy as np
+    import torch
+
+    from alpenglow_amd import rs
+
+    n, stride = args.slices, 64 * 1024
+    g = torch.Generator(device="cpu").manual_seed(0xF011)
+    pick = torch.argsort(torch.rand((n, 64), generator=g), dim=1)[:, :32]
+    keep = torch.zeros((n, 64), dtype=torch.bool).scatter_(1, pick, True).reshape(-1).to(dev)
+    got = lens * keep  # the received lengths, var layout
+    ord_t = torch.from_numpy(order).to(dev)
+    rows = (ord_t[:, None] * 64 + torch.arange(64, device=dev)[None, :]).reshape(-1)  # datagram rows, sorted by size
+    spk = torch.empty_like(pkts)
+    slens, sgot = torch.empty_like(lens), torch.empty_like(lens)
+    srt = mix[order]
+    offs = np.r_[0, np.cumsum(64 * srt.astype(np.int64))]  # codewords of the sorted slices, packed at 64 S
+    cwu = torch.zeros(int(offs[-1]), dtype=torch.uint8, device=dev)
+
+    def regroup():
+        torch.index_select(pkts, 0, rows, out=spk)
+        torch.index_select(got, 0, rows, out=sgot)
+
+    def var():
+        return [rs.shredder_deshred_batch_var(ctx, n, mix, pkts, PKT, lens, pk, cw, stride)]
+
+    def per_size():
+        return [rs.shredder_deshred_batch(ctx, e - b, int(srt[b]), spk[64 * b:64 * e], PKT, slens[64 * b:64 * e], pk,
+                                          cwu.data_ptr() + int(offs[b])) for b, e in zip(starts[:-1], starts[1:])]
+
+    def runs():
+        regroup()
+        slens.copy_(sgot)
+        return per_size()
+
+    pkts_u, lens_u, cw_u = torch.empty_like(pkts), torch.empty_like(lens), torch.empty_like(cw)
+    held = pkts.clone(), lens.clone()
+    shred_1024()  # maximum slices into pkts / lens, moved aside; then the block's datagrams back
+    torch.cuda.synchronize()
+    pkts_u.copy_(pkts)
+    got_u = lens * keep
+    pkts.copy_(held[0])
+    lens.copy_(held[1])
+    del held
+
+    def uniform():
+        return [rs.shredder_deshred_batch(ctx, n, 1024, pkts_u, PKT, lens_u, pk, cw_u)]
+
+    regroup()
+    legs = {"var_mix": (var, lambda: lens.copy_(got)), "presorted_mix": (per_size, lambda: slens.copy_(sgot)),
+            "runs_mix": (runs, lambda: None), "uniform_1024": (uniform, lambda: lens_u.copy_(got_u))}
+    res, times = {}, {k: [] for k in legs}
+    for step in range(max(args.warmup, 2) + args.steps):
+        for k, (f, reset) in legs.items():
+            reset()
+            out = []
+            t = timed(lambda: out.extend(f()))
+            res[k] = out
+            if step >= max(args.warmup, 2):
+                times[k].append(t)
+    ok = {k: all(bool((r.status == 0).all()) for r in v) for k, v in res.items()}
+    r = res["var_mix"][0]
+    same = bool((r.data_offsets == 9).all()) and bool((r.data_lens == dmix).all())
+    dl = torch.from_numpy(dmix.astype(np.int64)).to(dev)
+    col = torch.arange(32 * 1024 - 10, device=dev)[None, :]
+    cwv = cw.view(n, stride)
+    for b in range(0, n, 4096):  # payload bytes against the input, a few thousand slices at a time
+        e = min(n, b + 4096)
+        same = same and bool(((cwv[b:e, 9:9 + col.shape[1]] == data[b:e, :col.shape[1]]) | (col >= dl[b:e, None])).all())
+    out = {k: {"wall_ms": statistics.median(v), "slices_per_s": n / (statistics.median(v) * 1e-3), "steps": len(v)}
+           for k, v in times.items()}
+    return {"metric": "slices/s composed RegularShredder deshred over a block's mix of shred sizes from a random 32 "
+                      "of 64 datagrams per slice, one var call",
+            "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "legs": out,
+            "ratios": {"var_mix_over_runs_mix": out["runs_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
+                       "var_mix_over_presorted_mix": out["presorted_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
+                       "var_mix_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_mix"]["wall_ms"]},
+            "verify": {"every_status_ok": ok, "var_mix_payloads_equal_input": same}}
 
 
 def main():

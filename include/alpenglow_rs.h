@@ -571,6 +571,32 @@ int ag_shredder_shred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint8_t* p
                                 uint8_t* sigs_out, uint8_t* packets, size_t packet_stride, uint32_t* packet_lens,
                                 size_t nblocks, const uint32_t* block_counts, uint8_t* block_hashes_out);
 
+/* deshred_batch_var -- Shredder::deshred over slices that each have their own shred size, in
+ * the layout of ag_shredder_shred_batch_var: slice s owns the 64 datagram slots packets + (64 s
+ * + j) * packet_stride, and its 64 raw shreds are packed with stride S_s = shred_bytes[s] at
+ * codewords + s * codeword_stride (16-byte aligned, codeword_stride % 16 == 0); the parsed data
+ * is at codewords + s * codeword_stride + data_offsets_out[s].  shred_bytes (HOST, nslices)
+ * comes from the caller: a follower knows S_s from any stored datagram of the slice, its length
+ * minus ag_shred_datagram_bytes(0, 6).  For every slice, every output (status, header, parent,
+ * data offset and length, the codeword bytes, the datagram slots, packet_lens) is what
+ * ag_shredder_deshred_batch gives when run on that slice alone with S = S_s; the number of
+ * launches does not depend on the mix of sizes (but for the one-by-one EXACT re-run of failed
+ * slices with surplus shreds).  A datagram in a slot of slice s whose data length is not S_s
+ * counts as absent, so a slice given the wrong S_s ends as NOT_ENOUGH_SHARDS, never as a
+ * whole-call error.  No byte of a slice's codeword stride past 64 * S_s is written, no byte of
+ * a datagram slot past the length written there, and no present datagram; absent slots of
+ * failed slices keep their length 0 (their bytes are unspecified).
+ * Errors (nothing launched, nothing written), all INVALID_ARGUMENT: a null pointer with
+ * nslices > 0, an S_s of zero, odd or above 1024, codeword_stride < 64 * max S_s, codewords or
+ * codeword_stride no multiple of 16, packet_stride < ag_shred_datagram_bytes(max S_s, 6),
+ * nslices >= 2^24.  nslices == 0 returns AG_RS_OK.  Synchronous. */
+int ag_shredder_deshred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint32_t* shred_bytes /* HOST */,
+                                  uint8_t* packets, size_t packet_stride, uint32_t* packet_lens,
+                                  const uint8_t* pk, uint8_t* codewords, size_t codeword_stride,
+                                  int32_t* status, uint64_t* slots_out, uint64_t* slice_indices_out,
+                                  uint8_t* is_last_out, uint8_t* parent_flags_out, uint8_t* parent_ids_out,
+                                  uint32_t* data_offsets_out, uint32_t* data_lens_out);
+
 /* The other shredders of shredder.rs, composed the same way (round 6):
  *   AG_SHREDDER_CODING_ONLY  CodingOnlyShredder (:361-394): ReedSolomonCoder::new(64), the 64
  *                            coding shreds are the output (no data shreds);
