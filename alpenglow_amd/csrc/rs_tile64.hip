@@ -8,6 +8,7 @@
 //                      encode (the headline), LowRate encode / decode per 32-point chunk
 //   xform8_kernel      the same transform on 8 waves x 4 slots with epoch-flag swaps (tile body
 //                      in rs_xform8.hpp): decode from a full recovery set, small batches
+//   xform8_stream_kernel   xform8 with the streamed intake: the 32:32 full-recovery reconstruct
 //   decode_x_kernel    W = 32 window decoder on xform_kernel's layout
 //   decode_x16_kernel  W = 64 / 128 window decoder on 16 waves x 4 slots, one pattern per tile
 //   encode_mc_kernel, decode_syn_kernel   chunk <= 4 (16:4): one wave per tile, no LDS
@@ -98,6 +99,17 @@ __global__ __launch_bounds__(512, 4) void xform8_kernel(const XformParams p) {
   if (threadIdx.x < 16) reinterpret_cast<uint32_t*>(&flags)[threadIdx.x] = 0;
   __syncthreads();
   xform8_tile<DIN, DOUT, HALF, TAIL>(p, dev::xcd_tile(blockIdx.x, gridDim.x), lds, &flags);
+}
+
+// xform8_kernel on the streamed intake (xform8_stream_tile, rs_xform8.hpp): every input shard
+// exists, whole chunks, store masks given
+template <int DIN, int DOUT, bool HALF>
+__global__ __launch_bounds__(512, 4) void xform8_stream_kernel(const XformParams p) {
+  __shared__ uint4 lds[16 * 4 * kXfLanes];  // 8 waves x 2 slots x 4 KiB
+  __shared__ X8Flags flags;
+  if (threadIdx.x < 16) reinterpret_cast<uint32_t*>(&flags)[threadIdx.x] = 0;
+  __syncthreads();
+  xform8_stream_tile<DIN, DOUT, HALF>(p, dev::xcd_tile(blockIdx.x, gridDim.x), lds, &flags);
 }
 
 // =====================================================================================
@@ -797,6 +809,15 @@ hipError_t launch_xform(XformKind kind, const XformParams& p, hipStream_t stream
           hipLaunchKernelGGL((xform8_kernel<0, 32, true, 1>), grid, dim3(512), 0, stream, p);
         else
           hipLaunchKernelGGL((xform8_kernel<0, 32, false, 1>), grid, dim3(512), 0, stream, p);
+        break;
+      }
+      // the full recovery set of a 32:32 code (every input shard exists) with store masks: the
+      // streamed intake (headline reconstruct 1.09 -> 1.03-1.04 ms, profiles/stream_intake_ab.txt)
+      if (p.n_in == 32 && p.out_mask) {
+        if (p.out_low_half)
+          hipLaunchKernelGGL((xform8_stream_kernel<0, 32, true>), grid, dim3(512), 0, stream, p);
+        else
+          hipLaunchKernelGGL((xform8_stream_kernel<0, 32, false>), grid, dim3(512), 0, stream, p);
         break;
       }
       if (p.out_low_half)

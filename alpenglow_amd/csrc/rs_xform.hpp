@@ -507,6 +507,30 @@ __device__ __forceinline__ void xf_load_raw(const XformParams& p, const TileIO& 
   });
 }
 
+// Streamed intake (xform8_stream_tile: every input shard exists, no tail): the NS x 4 loads
+// of a wave's slots with no control flow between them, so the conversion of slot t waits for its
+// own four pieces only (s_waitcnt vmcnt(4 (NS - 1 - t))) and runs while the later slots are
+// still in flight.  With a branch per slot (s < n_in) or per piece (partial tiles) the first
+// conversion waits for the whole tile (vmcnt(0)).  Idle pieces of a batch-end tile re-read the
+// tile's first chunk (tile_io_g) and never store.  xform_kernel keeps xf_load_raw: the same
+// intake measured neutral on the headline encode.
+template <int NS>
+__device__ __forceinline__ void load_slots_stream(const XformParams& p, const TileIO& io, uint32_t s0,
+                                                  uint32_t (*raw)[16]) {
+  static_for<NS>([&](auto T) {
+    constexpr int t = decltype(T)::value;
+    const uint8_t* base = p.in + (s0 + t) * p.in_shard_stride;
+    static_for<4>([&](auto Q) {
+      constexpr int q = decltype(Q)::value;
+      const uint4 x = ld_piece(base + io.off[q]);
+      raw[t][4 * q] = x.x;
+      raw[t][4 * q + 1] = x.y;
+      raw[t][4 * q + 2] = x.z;
+      raw[t][4 * q + 3] = x.w;
+    });
+  });
+}
+
 // Planes -> bytes -> lane-linear pieces, stored where the input pieces were read.  ACC: XOR
 // into the bytes already there (a partial result stored by an earlier pass).
 template <bool ACC = false, int TAIL = 0>

@@ -1,6 +1,7 @@
 // xform8's tile body: the 32-point transform of one 64-column tile on 8 waves x 4 slots
 // (layouts and swaps in rs_xform.hpp).  Shared by xform8_kernel's grid and the per-call
-// server's transform jobs (both in rs_tile64.hip).  gfx950 / CDNA4 only.
+// server's transform jobs (both in rs_tile64.hip); xform8_stream_tile is the same transform
+// behind the streamed intake (xform8_stream_kernel).  gfx950 / CDNA4 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -140,6 +141,106 @@ __device__ __forceinline__ void xform8_tile(const XformParams& p, uint32_t tile,
     const uint32_t sh = 4 * wave + t;  // wave-uniform
     if (((need >> t) & 1u) && sh < p.n_out)
       store_shard<false, TAIL>(p.out + sh * p.out_shard_stride, out_io, (qall >> (4 * t)) & 15u, r[t]);
+  });
+}
+
+// xform8_tile with the streamed intake, for launches where every input shard exists, shards are
+// whole chunks and store masks are given (launch_xform: the 32:32 full-recovery reconstruct):
+//   - the tile's 16 loads per lane are issued with no control flow between them and slot t is
+//     converted behind s_waitcnt vmcnt(4 (3 - t)), a layer-0 butterfly behind its two slots
+//     (load_slots_stream; xform8_tile's first conversion waits for the whole tile);
+//   - the store-mask words are loaded ahead of the pieces and folded into the store predicates
+//     while the pieces are in flight: one VGPR lives across the transform, and no load sits
+//     between the last swap and the stores (xform8_tile fetches the words there: a dependent
+//     round trip per wave with nothing in flight to hide it).
+// The transform is xform8_tile's, written out again: shared through one template, the tiles
+// that keep the old intake (and the server's) compile to different instructions.
+template <int DIN, int DOUT, bool HALF>
+__device__ __forceinline__ void xform8_stream_tile(const XformParams& p, uint32_t tile, uint4* lds, X8Flags* fl) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const TileIO io = tile_io<0>(p, tile, lane, p.in_block_stride);
+  Regs4 r;
+  // One pattern for the batch reads word 0 through the same four loads (index masked, not
+  // branched: after a branch the words merge in a phi, and its copies wait for them before the
+  // first piece is requested).  A chunk's block and validity do not depend on the block stride:
+  // the input io's are the output's.
+  uint64_t mask[4];
+  const uint64_t per_block = p.pattern_per_block ? ~0ull : 0ull;
+  static_for<4>([&](auto Q) { mask[decltype(Q)::value] = p.out_mask[io.blk[decltype(Q)::value] & per_block]; });
+  load_slots_stream<4>(p, io, 4 * wave, r);
+  // store predicates packed before the first store (see qmask_all): here, before the transform
+  uint32_t qall;
+  if constexpr (HALF) qall = qmask_all<2>(io, mask, 2 * wave, p.n_out);
+  else qall = qmask_all<4>(io, mask, 4 * wave, p.n_out);
+  {
+    using L0 = X8Layout<0>;
+    const int v = x8_compress<L0::rel(0)>(wave);
+    static_for<2>([&](auto I) {
+      constexpr int t = 2 * decltype(I)::value;
+      static_for<2>([&](auto U) {
+        swap_halves(r[t + decltype(U)::value]);
+        dev::planes_from_raw(r[t + decltype(U)::value]);
+      });
+      x8_bfly_w<L0, 0, true, DIN, t>(v, r[t], r[t + 1]);
+    });
+  }
+  x8_layer<0, 1, true, DIN>(wave, r);
+  x8_swap<0, 0, 1>(wave, lane, lds, fl, r);
+  x8_layer<1, 2, true, DIN>(wave, r);
+  x8_swap<1, 1, 2>(wave, lane, lds, fl, r);
+  x8_layer<2, 3, true, DIN>(wave, r);
+  x8_swap<0, 2, 3>(wave, lane, lds, fl, r);
+  if constexpr (HALF) {
+    using H3 = X8Lay<4, 3, 0, 1, 2>;
+    using H2 = X8Lay<4, 2, 0, 1, 3>;
+    using H1 = X8Lay<4, 1, 0, 2, 3>;
+    using H0 = X8Lay<4, 0, 1, 2, 3>;
+    x8_layer<3, 4, true, DIN>(wave, r);
+    x8_layer<3, 4, false, DOUT, 0x5, false>(wave, r);
+    x8_layer_lay<H3, 3, DOUT, 0x5>(wave, r);
+    x8_swap<1, 2, 4, 0x5>(wave, lane, lds, fl, r);
+    x8_layer_lay<H2, 2, DOUT, 0x5>(wave, r);
+    x8_swap<1, 1, 5, 0x5>(wave, lane, lds, fl, r);
+    x8_layer_lay<H1, 1, DOUT, 0x5>(wave, r);
+    x8_swap<1, 0, 6, 0x5>(wave, lane, lds, fl, r);
+    const TileIO out_io = tile_io<0>(p, tile, lane, p.out_block_stride);
+    if (__builtin_amdgcn_ballot_w64(qall != 0) == 0) return;
+    x8_layer_lay<H0, 0, DOUT, 0x5>(wave, r);
+    static_for<2>([&](auto U) {
+      constexpr int t = 2 * decltype(U)::value;
+      const uint32_t sh = 2 * wave + (t >> 1);  // H0 position of live slot t
+      if (sh < p.n_out) store_shard(p.out + sh * p.out_shard_stride, out_io, (qall >> (4 * (t >> 1))) & 15u, r[t]);
+    });
+    return;
+  }
+  x8_layer<3, 4, true, DIN>(wave, r);
+  x8_layer<3, 4, false, DOUT>(wave, r);
+  x8_layer<3, 3, false, DOUT>(wave, r);
+  x8_swap<0, 2, 4>(wave, lane, lds, fl, r);
+  x8_layer<2, 2, false, DOUT>(wave, r);
+  x8_swap<1, 1, 5>(wave, lane, lds, fl, r);
+  x8_layer<1, 1, false, DOUT>(wave, r);
+  x8_swap<0, 0, 6>(wave, lane, lds, fl, r);
+  const TileIO out_io = tile_io<0>(p, tile, lane, p.out_block_stride);
+  // slots some lane stores (wave-uniform), as in xform8_tile
+  uint32_t need = 0;
+  static_for<4>([&](auto T) {
+    constexpr int t = decltype(T)::value;
+    if (__builtin_amdgcn_ballot_w64(((qall >> (4 * t)) & 15u) != 0) != 0) need |= 1u << t;
+  });
+  if (need == 0) return;
+  {
+    using L0 = X8Layout<0>;
+    const int v = x8_compress<L0::rel(0)>(wave);
+    if (need & 3u) x8_bfly_w<L0, 0, false, DOUT, 0>(v, r[0], r[1], (need & 2u) != 0);
+    if (need & 12u) x8_bfly_w<L0, 0, false, DOUT, 2>(v, r[2], r[3], (need & 8u) != 0);
+  }
+  static_for<4>([&](auto T) {
+    constexpr int t = decltype(T)::value;
+    const uint32_t sh = 4 * wave + t;  // wave-uniform
+    if (((need >> t) & 1u) && sh < p.n_out)
+      store_shard(p.out + sh * p.out_shard_stride, out_io, (qall >> (4 * t)) & 15u, r[t]);
   });
 }
 

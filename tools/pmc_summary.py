@@ -25,7 +25,8 @@ for f in sorted(glob.glob(os.path.join(args.dir, "p*", "pmc_counter_collection.c
         name = r["Kernel_Name"]
         # (xform_kernel<4, ...>: the name in profiles taken before its wave-count parameter was dropped)
         short = "encode" if any(k in name for k in ("xform8_kernel<32, 0", "xform_kernel<32, 0", "xform_kernel<4, 32, 0")) else \
-                "reconstruct" if any(k in name for k in ("xform8_kernel<0, 32", "xform_kernel<0, 32", "xform_kernel<4, 0, 32")) else \
+                "reconstruct" if any(k in name for k in ("xform8_stream_kernel<0, 32", "xform8_kernel<0, 32", "xform_kernel<0, 32",
+                                                         "xform_kernel<4, 0, 32")) else \
                 (re.search(r"(\w+(<[^()]*>)?)\(", name.replace("(anonymous namespace)", "")) or
                  re.search(r"(\w+)", name)).group(1)[:60]
         vals[short][r["Counter_Name"]].append(float(r["Counter_Value"]))

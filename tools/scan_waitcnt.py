@@ -16,6 +16,8 @@ text-order neighbour.  Reports carry the ISA line number.
 
 Usage: python tools/scan_waitcnt.py [--window W] [source.hip | file.s ...]
        (default: the RS kernel sources, compiled to gfx950 assembly)
+       python tools/scan_waitcnt.py --intake NAME [source.hip | file.s ...]
+       (the tile intake of the kernels matching NAME: where the first conversion waits)
 """
 import argparse
 import os
@@ -134,6 +136,46 @@ def scan(asm: str, window: int):
     return out
 
 
+def intake(asm: str, name: str):
+    """--intake: per kernel whose symbol contains `name`, the ISA from the first vector load to
+    the first ds_write_b128 in text order, reduced to runs of vector loads (the tile's pieces
+    are global_load_dwordx4), vmcnt waits, runs of v_permlane32_swap (a slot's conversion
+    starts with them) and control flow (runs of branches and labels as one `branches`)."""
+    out = []
+    for m in re.finditer(r"^(_Z\S+):", asm, re.M):
+        if name not in m.group(1):
+            continue
+        ev, started = [], False
+
+        def add(what):
+            if ev and ev[-1][0] == what:
+                ev[-1][1] += 1
+            else:
+                ev.append([what, 1])
+
+        for raw in asm[m.end():asm.find(".Lfunc_end", m.end())].splitlines():
+            t = raw.split(";")[0].strip()
+            if not t or (t.startswith(".") and not t.startswith(".LBB")):
+                continue
+            op = t.split()[0]
+            if not started and kind(t) != "L":
+                continue
+            started = True
+            if kind(t) == "L":
+                add(op)
+            elif op == "s_waitcnt" and "vmcnt(" in t:
+                ev.append([re.search(r"vmcnt\(\d+\)", t).group(0), 1])
+            elif op.startswith("v_permlane32_swap"):
+                add("swap")
+            elif op in ("s_branch", "s_endpgm") or op.startswith("s_cbranch") or t.startswith(".LBB"):
+                if not ev or ev[-1][0] != "branches":
+                    ev.append(["branches", 1])
+            elif op == "ds_write_b128":
+                break
+        out.append((m.group(1), " ".join(w if w.startswith(("vmcnt", "branches")) else f"{n}x{w}" for w, n in ev)))
+    return out
+
+
 def to_asm(src, d):
     if src.endswith(".s"):
         return open(src).read()
@@ -151,9 +193,16 @@ def main():
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("srcs", nargs="*", default=["rs_tile64.hip", "rs_window.hip", "rs_generic.hip", "rs_coder_kernels.hip",
                                                  "rs_xform64.hip", "rs_decode_c.hip"])
+    ap.add_argument("--intake", metavar="NAME", help="print the load / wait sequence of the kernels whose symbol "
+                    "contains NAME, first tile load to first ds_write_b128, instead of scanning")
     args = ap.parse_args()
     total = 0
     with tempfile.TemporaryDirectory() as d:
+        if args.intake is not None:
+            for src in args.srcs:
+                for name, seq in intake(to_asm(src, d), args.intake):
+                    print(f"{os.path.basename(src)}: {name}\n    {seq}")
+            return
         for src in args.srcs:
             for name, reps in scan(to_asm(src, d), args.window):
                 kinds = {}
