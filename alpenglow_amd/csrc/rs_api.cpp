@@ -197,6 +197,16 @@ int ag_rs_internal_last_merkle_kernels(ag_rs_ctx* c, uint32_t* out) {
   return AG_RS_OK;
 }
 
+// Test aid (not in the header): out[0] = the slices the last composed deshred call on this
+// context (ag_shredder_deshred_batch / _var / _kind) decoded again with EXACT, out[1] = the
+// batched EXACT coder passes it made for them.
+int ag_rs_internal_last_exact_rerun(ag_rs_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return AG_RS_ERR_INVALID_ARGUMENT;
+  out[0] = c->last_rerun_slices;
+  out[1] = c->last_rerun_passes;
+  return AG_RS_OK;
+}
+
 int ag_rs_has_fast_path(size_t k, size_t m, size_t S) {
   // shard sizes that are not whole 64-byte chunks run restrided (padded) on the same kernels
   if (S == 0 || S % 2) return 0;
@@ -2123,9 +2133,12 @@ int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_
 // strip, the store masks, and the re-encode when `reencode` (some slice has surplus shreds or
 // every data shred; otherwise every store mask is zero).  Synchronous: plen[s] on return.  The
 // caller has reset last_encode_kernels / last_window_kernels.
+// exact: the crate's decoder over every kept shred instead (launch_pipe_patterns' exact masks, no
+// fused coding restore): the same kernels -- var_decode runs the full 64-point window whatever
+// the masks, and the store masks re-encode every coding shred of a surplus slice.
 int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
                            const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
-                           bool reencode, int64_t* plen) {
+                           bool reencode, int64_t* plen, bool exact) {
   int st;
   if ((st = pipe_coder_reserve(c, n, kDataShreds))) return st;
   uint64_t* xm = c->xmask.dev.as<uint64_t>();
@@ -2133,7 +2146,7 @@ int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride
   uint8_t* few = c->d_pipe_few.as<uint8_t>();
   uint64_t* mask = c->d_pipe_mask.as<uint64_t>();
   int64_t* strip = c->d_strip.as<int64_t>();
-  if (ag::launch_pipe_patterns(d_present, n, xm, few, true, c->stream) != hipSuccess ||
+  if (ag::launch_pipe_patterns(d_present, n, xm, few, true, c->stream, exact) != hipSuccess ||
       ag::launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), 64, c->dtables(), rows, true, c->stream) !=
           hipSuccess)
     return AG_RS_ERR_DEVICE;

@@ -176,8 +176,11 @@ struct ag_rs_ctx {
   PinBuf h_strip;                           // coder deshred batches: pinned staging of the results
   PinBuf h_slice_meta;                      // slice parse batches: pinned staging of the results
   PinBuf h_pipe_meta;                       // composed deshreds: pinned staging of the per-slice columns
+  PinBuf h_rerun;                           // their EXACT re-run: pinned staging of the list | sizes | column prefix
+  hipEvent_t rerun_ev = nullptr;            // recorded after its upload
+  uint64_t last_rerun_slices = 0, last_rerun_passes = 0;  // the last composed deshred's EXACT re-run (test aid)
   DevBuf d_ed_base;                         // Ed25519 fixed-base table (ed25519.hpp)
-  static constexpr int kPipeBufs = 33;
+  static constexpr int kPipeBufs = 37;
   DevBuf pipe[kPipeBufs];                   // composed shredder scratch (shredder_api.cpp's PipeBuf roles)
   DevBuf d_sh_roots, d_sh_commit, d_sh_onvalid, d_sh_list;  // shred validation scratch
   // host-memory calls: two staging slots, H2D / D2H streams next to the compute stream
@@ -345,6 +348,11 @@ struct ag_rs_ctx {
     h_strip.release();
     h_slice_meta.release();
     h_pipe_meta.release();
+    if (rerun_ev) {
+      (void)hipEventSynchronize(rerun_ev);
+      (void)hipEventDestroy(rerun_ev);
+    }
+    h_rerun.release();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 };
@@ -385,7 +393,7 @@ int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_
                        int64_t* plen, size_t m, bool no_surplus = false);
 int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
                            const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
-                           bool reencode, int64_t* plen);
+                           bool reencode, int64_t* plen, bool exact = false);
 int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t** d_sizes, const uint32_t** d_col_base,
                      uint32_t* total_columns);
 bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "shredder.hpp"
+#include "unaligned.hpp"
 
 namespace ag {
 namespace {
@@ -152,9 +153,11 @@ __device__ __forceinline__ uint64_t keep_lowest(uint64_t b, uint32_t budget) {
 // (reed_solomon.rs:206) -- few[s] bit 1 marks them, and the separate re-encode skips them.
 // Slices with surplus kept shreds keep the re-encode (present-but-unused recovery shreds are
 // rewritten only when the slice succeeds).  few[s] bit 0: fewer than k kept shreds.
+// exact: the crate's decoder instead (reed_solomon.rs:154-166 adds every kept shred): every kept
+// position is loaded, only the absent ones are erased, the absent data shreds are restored.
 __global__ __launch_bounds__(256) void pipe_patterns_kernel(const uint64_t* __restrict__ present, uint64_t n,
                                                             uint64_t* __restrict__ xm, uint8_t* __restrict__ few,
-                                                            uint32_t fuse) {
+                                                            uint32_t fuse, uint32_t exact) {
   const uint64_t s = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const uint64_t pr = present[s];
@@ -164,7 +167,7 @@ __global__ __launch_bounds__(256) void pipe_patterns_kernel(const uint64_t* __re
   uint64_t in = 0, out = 0, e = 0;
   uint8_t f = cnt < kPipeData ? 1 : 0;
   if (cnt >= kPipeData && ob != 0xFFFFFFFFull) {
-    rb = keep_lowest(rb, kPipeData - static_cast<uint32_t>(__builtin_popcountll(ob)));
+    if (!exact) rb = keep_lowest(rb, kPipeData - static_cast<uint32_t>(__builtin_popcountll(ob)));
     in = rb | (ob << 32);
     out = (~ob & 0xFFFFFFFFull) << 32;
     e = (~rb & 0xFFFFFFFFull) | out;
@@ -253,6 +256,64 @@ __global__ __launch_bounds__(256) void pipe_leaf_flags_kernel(const uint64_t* __
   flags[t] = (!((pr >> j) & 1) || (j >= kPipeData && coding_rewritten)) ? 1 : 0;
 }
 
+// dst[0, len) = src[0, len) at any alignment of either (wire.hip's copy16_any): 16-byte lane
+// accesses, the last len % 16 bytes singly.  One wave.
+__device__ __forceinline__ void rerun_copy(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, uint32_t len,
+                                           uint32_t lane) {
+  const uint32_t n16 = len >> 4;
+  for (uint32_t i = lane; i < n16; i += 64) st16u(dst + 16 * i, ld16u(src + 16 * i));
+  for (uint32_t i = 16 * n16 + lane; i < len; i += 64) dst[i] = src[i];
+}
+// the output shred held by codeword row `row` of the layout (row0, skip), or kPipeNone
+__device__ __forceinline__ uint32_t rerun_shred_of_row(const PipeRerunParams& p, uint32_t row) {
+  if (row < p.row0) return kPipeNone;
+  const uint32_t q = row - p.row0;
+  if (p.skip && q == p.skip) return kPipeNone;
+  const uint32_t j = p.skip && q > p.skip ? q - 1 : q;
+  return j < kPipeShreds ? j : kPipeNone;
+}
+
+// One wave per (listed slice r, codeword row): the row of slice s = list[r] as the datagrams
+// hold it (a kept shred: its payload, at kShredHeadBytes of its slot) or as the codeword holds
+// it (every other row), into row `row` of compact codeword r.  The first row's wave also copies
+// the slice's kept-shred word and signed root.
+__global__ __launch_bounds__(256) void pipe_rerun_gather_kernel(const PipeRerunParams p) {
+  const uint64_t w = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (w >= static_cast<uint64_t>(p.nlist) * p.rows) return;
+  const uint32_t r = static_cast<uint32_t>(w / p.rows), row = static_cast<uint32_t>(w % p.rows);
+  const uint64_t s = p.list[r];
+  const uint32_t S = p.sizes[r];
+  const uint64_t pr = p.present[s];
+  const uint32_t j = rerun_shred_of_row(p, row);
+  const uint8_t* src = j != kPipeNone && ((pr >> j) & 1)
+                           ? p.packets + (s * kPipeShreds + j) * p.packet_stride + kShredHeadBytes
+                           : p.codewords + s * p.cw_stride + static_cast<uint64_t>(row) * S;
+  rerun_copy(p.compact + r * p.compact_stride + static_cast<uint64_t>(row) * S, src, S, lane);
+  if (row == 0) {
+    if (lane == 0) p.c_present[r] = pr;
+    if (lane < 32) p.c_sroot[32 * static_cast<uint64_t>(r) + lane] = p.sroot[32 * s + lane];
+  }
+}
+
+// The inverse after the pass: compact codeword r's rows (rows * S bytes, nothing past them),
+// its 64 proof rows and its rebuilt root back to slice list[r]'s places.
+__global__ __launch_bounds__(256) void pipe_rerun_scatter_kernel(const PipeRerunParams p) {
+  const uint64_t w = static_cast<uint64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (w >= static_cast<uint64_t>(p.nlist) * p.rows) return;
+  const uint32_t r = static_cast<uint32_t>(w / p.rows), row = static_cast<uint32_t>(w % p.rows);
+  const uint64_t s = p.list[r];
+  const uint32_t S = p.sizes[r];
+  rerun_copy(p.codewords + s * p.cw_stride + static_cast<uint64_t>(row) * S,
+             p.compact + r * p.compact_stride + static_cast<uint64_t>(row) * S, S, lane);
+  if (row < kPipeShreds)
+    rerun_copy(p.proofs + (s * kPipeShreds + row) * p.proof_stride,
+               p.c_proofs + (static_cast<uint64_t>(r) * kPipeShreds + row) * p.proof_stride,
+               static_cast<uint32_t>(p.proof_stride), lane);
+  if (row == 0 && lane < 32) p.roots[32 * s + lane] = p.c_roots[32 * static_cast<uint64_t>(r) + lane];
+}
+
 }  // namespace
 
 hipError_t launch_pipe_expand(const PipeExpandParams& p, hipStream_t stream) {
@@ -304,10 +365,10 @@ hipError_t launch_pipe_merge_lens(const uint32_t* fresh, const uint64_t* present
 }
 
 hipError_t launch_pipe_patterns(const uint64_t* present, uint64_t nslices, uint64_t* xm, uint8_t* few, bool fuse,
-                                hipStream_t stream) {
+                                hipStream_t stream, bool exact) {
   if (nslices == 0) return hipSuccess;
   hipLaunchKernelGGL(pipe_patterns_kernel, grid256(nslices), dim3(256), 0, stream, present, nslices, xm, few,
-                     fuse ? 1u : 0u);
+                     fuse && !exact ? 1u : 0u, exact ? 1u : 0u);
   return hipGetLastError();
 }
 
@@ -332,6 +393,22 @@ hipError_t launch_pipe_leaf_flags(const uint64_t* present, uint64_t nslices, boo
   if (nslices == 0) return hipSuccess;
   hipLaunchKernelGGL(pipe_leaf_flags_kernel, grid256(nslices * kPipeShreds), dim3(256), 0, stream, present, nslices,
                      reencode_all ? 1u : 0u, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_pipe_rerun_gather(const PipeRerunParams& p, hipStream_t stream) {
+  const uint64_t waves = static_cast<uint64_t>(p.nlist) * p.rows;
+  if (waves == 0) return hipSuccess;
+  if ((waves + 3) / 4 > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pipe_rerun_gather_kernel, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_pipe_rerun_scatter(const PipeRerunParams& p, hipStream_t stream) {
+  const uint64_t waves = static_cast<uint64_t>(p.nlist) * p.rows;
+  if (waves == 0) return hipSuccess;
+  if ((waves + 3) / 4 > 0x7FFFFFFFull || p.rows < kPipeShreds) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pipe_rerun_scatter_kernel, dim3(static_cast<unsigned>((waves + 3) / 4)), dim3(256), 0, stream, p);
   return hipGetLastError();
 }
 

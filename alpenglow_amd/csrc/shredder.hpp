@@ -103,8 +103,10 @@ hipError_t launch_pipe_merge_lens(const uint32_t* fresh, const uint64_t* present
 // fuse (the packed window decoder, decode_pk<-1>): a slice with exactly 32 kept shreds also
 // restores its absent coding shreds in the decode (xm[n + 2 s + 1] = every erased position)
 // and gets few[s] = 2, so the re-encode's store mask skips it.
+// exact: the crate's decoder over every kept shred -- xm[n + 2 s] = every kept position, xm[s] =
+// every absent position and nothing else, xm[n + 2 s + 1] = the absent originals; never fused.
 hipError_t launch_pipe_patterns(const uint64_t* present, uint64_t nslices, uint64_t* xm, uint8_t* few, bool fuse,
-                                hipStream_t stream);
+                                hipStream_t stream, bool exact = false);
 // The same for CodingOnly slices (LowRate 32:64) in the W = 128 window of the two-pass decoder:
 // present[2 s] = data bits | coding 0..31 << 32, present[2 s + 1] = coding 32..63; xm =
 // decode_rows128's m6 [n][6], then the pass-1 and pass-2 (survivors, restored) pairs [n][2]
@@ -127,5 +129,40 @@ hipError_t launch_pipe_store_masks(const uint8_t* few, int64_t* strip, const uin
 // reencode_all); 0: its digest from the proof check stands.
 hipError_t launch_pipe_leaf_flags(const uint64_t* present, uint64_t nslices, bool reencode_all, uint8_t* flags,
                                   hipStream_t stream);
+
+
+// The batched EXACT re-run of the composed deshreds (shredder_api.cpp rerun_exact): the nlist
+// listed slices as a compact batch of codewords.  Slice s = list[r] has `rows` codeword rows of
+// sizes[r] bytes, packed at codewords + s * cw_stride and at compact + r * compact_stride;
+// output shred j sits in row row0 + j, one further from shred `skip` on (0: none) -- ShredderKind.
+struct PipeRerunParams {
+  const uint32_t* list;    // [nlist] the slices re-run, ascending
+  const uint32_t* sizes;   // [nlist] their shred sizes
+  uint32_t nlist;
+  uint32_t rows;           // 32 + m >= 64
+  uint32_t row0, skip;
+  uint8_t* codewords;      // the caller's
+  uint64_t cw_stride;
+  uint8_t* compact;
+  uint64_t compact_stride;  // >= rows * max size
+  const uint8_t* packets;   // the datagram slots (slice s: slots 64 s + j)
+  uint64_t packet_stride;
+  const uint64_t* present;  // [nslices] the kept shreds
+  const uint8_t* sroot;     // [nslices][32] their signed root
+  uint64_t* c_present;      // [nlist] gather out
+  uint8_t* c_sroot;         // [nlist][32] gather out
+  // scatter: the compact batch's rebuilt roots and proof rows, and the whole batch's
+  const uint8_t* c_roots;   // [nlist][32]
+  uint8_t* roots;           // [nslices][32]
+  const uint8_t* c_proofs;  // [nlist * 64][proof_stride]
+  uint8_t* proofs;          // [nslices * 64][proof_stride]
+  uint64_t proof_stride;
+};
+// Gather: every kept shred's payload out of its datagram slot (the failed pass rewrote restored
+// rows and decrypted in place), every other row as the codeword holds it, plus the kept-shred
+// words and signed roots.  Scatter: the rows (rows * sizes[r] bytes per slice, nothing past
+// them), proof rows and rebuilt roots back.  Grids follow nlist; nothing is launched for 0.
+hipError_t launch_pipe_rerun_gather(const PipeRerunParams& p, hipStream_t stream);
+hipError_t launch_pipe_rerun_scatter(const PipeRerunParams& p, hipStream_t stream);
 
 }  // namespace ag

@@ -76,6 +76,11 @@ enum PipeBuf : int {
   // per slice, shred side (callers that pass no roots_out / sigs_out)
   kBufSliceRoots,
   kBufSliceSigs,
+  // the batched EXACT re-run of a deshred (rerun_exact), per listed slice
+  kBufRerunList,       // list | sizes | column prefix (uint32)
+  kBufRerunCodewords,  // the compact codewords
+  kBufRerunMeta,       // signed roots | rebuilt roots | kept-shred words | root comparison
+  kBufRerunProofs,     // the rebuilt trees' 64 paths
   kPipeBufCount
 };
 static_assert(kPipeBufCount == ag_rs_ctx::kPipeBufs);
@@ -485,53 +490,125 @@ int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const 
   return AG_RS_OK;
 }
 
-// Step 6b of ag_shredder_deshred_batch for slice s: its datagram rows are parsed again into
-// the codeword (the pass before rewrote the restored and re-encoded rows), the kept shreds
-// (present bit mask) go through ReedSolomonCoder::deshred with the crate's EXACT decoder,
-// and the Merkle rebuild (roots2 row s, the slice's proof rows), root comparison and
-// SlicePayload parse are redone for this slice.  Outputs replace slice s's entries.
-// S: the slice's shred size; its 64 rows are packed at S from codewords + s * slice_stride (64 S
-// in the uniform call; with mixed sizes the rows are only 2-byte aligned, which the one-slice
-// uniform calls take: the byte copy of the parse, the byte-aligned leaf kernel).
-int pipe_rerun_exact(ag_rs_ctx* c, const ShredderKind& k, size_t s, size_t S, size_t slice_stride,
-                     const uint8_t* packets, size_t packet_stride, const uint32_t* packet_lens,
-                     const DeshredViews& v, uint8_t* codewords, uint8_t* same, int64_t* plen, uint8_t* h_same,
-                     uint8_t* sstat, uint8_t* parent_flag, uint8_t* parent_id, uint32_t* data_offset,
-                     uint32_t* data_len) {
-  constexpr size_t kRows = ag::kPipeShreds;
-  const size_t r0 = s * kRows, cw_stride = kRows * S;
-  uint8_t* cw = codewords + s * slice_stride;
-  ag::ShredColumns rc = v.cols;
-  rc.data_stride = S;  // one slice, its rows at t * S
-  rc.group_stride = 0;
-  rc.row_sizes = nullptr;
-  rc.kind += r0;
-  rc.slot += r0;
-  rc.slice_index += r0;
-  rc.is_last += r0;
-  rc.shred_index += r0;
-  rc.data = cw;
-  rc.data_len += r0;
-  rc.sig += 64 * r0;
-  rc.proof += r0 * v.cols.proof_stride;
-  rc.height += r0;
-  if (ag::launch_shred_deserialize(packets + r0 * packet_stride, packet_stride, packet_lens + r0, kRows, rc,
-                                   v.wire + r0, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  uint8_t dp[ag::kPipeData], cp[kRows - ag::kPipeData];
-  coder_flags(k, v.h.present[s], dp, cp);
-  int st = ag_rs_coder_deshred_batch(c, kRows - ag::kPipeData, 1, S, cw, cw_stride, dp, cp, AG_RS_DECODE_EXACT, plen);
-  if (st) return st;
-  *h_same = 0;
-  if (*plen < 0) return AG_RS_OK;
-  if ((st = ag_merkle_build_batch(c, kRows, S, 1, cw, S, cw_stride, v.roots2 + 32 * s, nullptr, 0,
-                                  v.cols.proof + r0 * v.cols.proof_stride, kRows * v.cols.proof_stride)))
+// What rerun_exact hands back for the listed slices, entry r for slice list[r]: the coder's
+// result, the root comparison and SlicePayload::try_from's outputs.
+struct RerunResult {
+  std::vector<int64_t> plen;
+  std::vector<uint8_t> same, sstat, parent_flag, parent_id;
+  std::vector<uint32_t> data_offset, data_len;
+};
+
+// Step 6b of the composed deshreds: the listed slices (ascending; each failed the padding or the
+// Merkle check of the ANY_K pass with more than 32 kept shreds) decoded again with the crate's
+// decoder over every kept shred, all of them in one pass over a compact batch.
+//   gather   the kept shreds' payloads out of their datagram slots (the pass before rewrote the
+//            restored and re-encoded rows, and PETS / AONT decrypted in place), every other row
+//            as the codeword holds it, the kept-shred words and the signed roots;
+//   coder    Regular: the mixed-size device stages with EXACT masks (pipe_coder_deshred_var),
+//            whatever the sizes -- a uniform call is the mix of one size, tails under 16 bytes
+//            included; the other shredders: ag_rs_coder_deshred_batch(EXACT), batched on its
+//            host-pattern route;
+//   checks   the Merkle rebuild over the raw output shreds (every leaf hashed), the root
+//            comparison, SlicePayload::try_from;
+//   scatter  the codeword rows (nothing past them), proof rows and rebuilt roots back to the
+//            slices' places.  The caller copies *out into the slices' entries.
+// S: the uniform shred size, or sizes (HOST, per slice of the whole batch; Regular only).
+// passed (nullable): set when some listed slice decoded and matches its signed root -- nothing is
+// scattered then, the caller redoes its batch.  (It does not happen: kept shreds that no decode
+// of 32 of them reproduces are no codeword, and no codeword's tree has their signed root.)
+int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>& list, size_t S,
+                const uint32_t* sizes, const uint8_t* packets, size_t packet_stride, const DeshredViews& v,
+                uint8_t* codewords, size_t cw_stride, RerunResult* out, bool* passed) {
+  const size_t R = list.size(), rows = kDataShreds + k.m;
+  const bool regular = k.aon < 0 && k.m == kDataShreds;
+  int st;
+  // list | sizes | column prefix through pinned staging, rewritten once its last upload completed
+  if (c->rerun_ev) AG_HIP(hipEventSynchronize(c->rerun_ev));
+  else AG_HIP(hipEventCreateWithFlags(&c->rerun_ev, hipEventDisableTiming));
+  const size_t words = 3 * R + 1;
+  if ((st = c->h_rerun.ensure(4 * words))) return st;
+  uint32_t* h = c->h_rerun.as<uint32_t>();
+  size_t max_s = 0;
+  uint32_t cols = 0;
+  for (size_t r = 0; r < R; ++r) {
+    const uint32_t Ss = sizes ? sizes[list[r]] : static_cast<uint32_t>(S);
+    h[r] = list[r];
+    h[R + r] = Ss;
+    h[2 * R + r] = cols;
+    cols += (Ss + 63) / 64;
+    max_s = std::max<size_t>(max_s, Ss);
+  }
+  h[3 * R] = cols;
+  const size_t cstride = (rows * max_s + 15) / 16 * 16;
+  uint8_t *d_list, *ccw, *meta, *c_proofs;
+  if ((st = pipe_buf(c, kBufRerunList, 4 * words, &d_list)) || (st = pipe_buf(c, kBufRerunCodewords, R * cstride, &ccw)) ||
+      (st = pipe_buf(c, kBufRerunMeta, (32 + 32 + 8 + 1) * R, &meta)) ||
+      (st = pipe_buf(c, kBufRerunProofs, R * ag::kPipeShreds * kPipeProofBytes, &c_proofs)))
     return st;
-  if (ag::launch_pipe_root_cmp(v.roots2 + 32 * s, v.sroot + 32 * s, 1, same + s, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
-  AG_HIP(hipMemcpyAsync(h_same, same + s, 1, hipMemcpyDeviceToHost, c->stream));
-  // synchronous: h_same has landed when it returns
-  return ag_slice_parse_batch(c, 1, cw, cw_stride, plen, sstat, parent_flag, parent_id, data_offset, data_len);
+  AG_HIP(hipMemcpyAsync(d_list, h, 4 * words, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipEventRecord(c->rerun_ev, c->stream));
+  const uint32_t* d_sizes = reinterpret_cast<const uint32_t*>(d_list) + R;
+  ag::PipeRerunParams rp{};
+  rp.list = reinterpret_cast<const uint32_t*>(d_list);
+  rp.sizes = d_sizes;
+  rp.nlist = static_cast<uint32_t>(R);
+  rp.rows = static_cast<uint32_t>(rows);
+  rp.row0 = k.row0;
+  rp.skip = k.skip;
+  rp.codewords = codewords;
+  rp.cw_stride = cw_stride;
+  rp.compact = ccw;
+  rp.compact_stride = cstride;
+  rp.packets = packets;
+  rp.packet_stride = packet_stride;
+  rp.present = v.d_present;
+  rp.sroot = v.sroot;
+  rp.c_sroot = meta;  // 32-byte rows first: the Merkle build wants 16-byte aligned roots
+  uint8_t* c_roots = meta + 32 * R;
+  rp.c_roots = c_roots;
+  rp.c_present = reinterpret_cast<uint64_t*>(meta + 64 * R);
+  uint8_t* c_same = meta + 72 * R;
+  rp.roots = v.roots2;
+  rp.c_proofs = c_proofs;
+  rp.proofs = v.cols.proof;
+  rp.proof_stride = kPipeProofBytes;
+  if (ag::launch_pipe_rerun_gather(rp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  out->plen.assign(R, 0);
+  if (regular) {
+    c->last_encode_kernels = 0;
+    c->last_window_kernels = 0;
+    if ((st = pipe_coder_deshred_var(c, R, ccw, cstride, rp.c_present, d_sizes, d_sizes + R, cols, true,
+                                     out->plen.data(), true)) ||
+        (st = merkle_var_launch(c, R, d_sizes, ccw, cstride, c_roots, nullptr, 0, c_proofs,
+                                ag::kPipeShreds * kPipeProofBytes)))
+      return st;
+  } else {
+    std::vector<uint8_t> dp(R * kDataShreds, 0), cp(R * k.m, 0);
+    for (size_t r = 0; r < R; ++r) coder_flags(k, v.h.present[list[r]], &dp[r * kDataShreds], &cp[r * k.m]);
+    if ((st = ag_rs_coder_deshred_batch(c, k.m, R, S, ccw, cstride, dp.data(), cp.data(), AG_RS_DECODE_EXACT,
+                                        out->plen.data())) ||
+        (st = kind_merkle(c, k, R, S, ccw, cstride, c_roots, c_proofs)))
+      return st;
+  }
+  c->last_rerun_slices = R;
+  c->last_rerun_passes = 1;
+  if (ag::launch_pipe_root_cmp(c_roots, rp.c_sroot, R, c_same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  out->same.assign(R, 0);
+  AG_HIP(hipMemcpyAsync(out->same.data(), c_same, R, hipMemcpyDeviceToHost, c->stream));
+  out->sstat.assign(R, 0);
+  out->parent_flag.assign(R, 0);
+  out->parent_id.assign(R * AG_SLICE_BLOCK_ID_BYTES, 0);
+  out->data_offset.assign(R, 0);
+  out->data_len.assign(R, 0);
+  if ((st = ag_slice_parse_batch(c, R, ccw, cstride, out->plen.data(), out->sstat.data(), out->parent_flag.data(),
+                                 out->parent_id.data(), out->data_offset.data(), out->data_len.data())))
+    return st;  // synchronous: the comparison has landed
+  for (size_t r = 0; r < R; ++r) {
+    if (out->plen[r] < 0) out->same[r] = 0;
+    if (passed && out->same[r]) *passed = true;
+  }
+  if (passed && *passed) return AG_RS_OK;
+  return ag::launch_pipe_rerun_scatter(rp, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
 
 // RegularShredder's deshred, the body of ag_shredder_deshred_batch (sizes null: every shred S
@@ -548,6 +625,7 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
   int st;
   ShredderKind k;
   shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
+  c->last_rerun_slices = c->last_rerun_passes = 0;
   const uint32_t *d_sizes = nullptr, *d_col_base = nullptr;
   uint32_t total_columns = 0;
   if (sizes) {
@@ -652,16 +730,29 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
   //     Merkle check with more than 32 kept shreds may hold an inconsistent shred the ANY_K
   //     pass did not read (a leader signing a non-codeword), and the crate's bytes -- hence
   //     the error, BadEncoding vs InvalidMerkleTree -- can differ.  Such slices are decoded
-  //     again from their received bytes with EXACT and re-checked, one by one (honest
-  //     leaders never produce them).
+  //     again from their received bytes with EXACT and re-checked, all of them in one batched
+  //     pass (rerun_exact; honest leaders never produce them: nothing is launched then).
+  std::vector<uint32_t> rerun;
   for (size_t s = 0; s < n; ++s) {
     const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
-    if (!failed || __builtin_popcountll(h_present[s]) <= static_cast<int>(ag::kPipeData)) continue;
-    if ((st = pipe_rerun_exact(c, k, s, sizes ? sizes[s] : S, cw_stride, packets, packet_stride, packet_lens, v, codewords, same, &plen[s],
-                               &h_same[s], &sstat[s], parent_flags_out + s,
-                               parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s, data_offsets_out + s,
-                               data_lens_out + s)))
+    if (failed && __builtin_popcountll(h_present[s]) > static_cast<int>(ag::kPipeData))
+      rerun.push_back(static_cast<uint32_t>(s));
+  }
+  if (!rerun.empty()) {
+    RerunResult rr;
+    if ((st = rerun_exact(c, k, rerun, S, sizes, packets, packet_stride, v, codewords, cw_stride, &rr, nullptr)))
       return st;
+    for (size_t r = 0; r < rerun.size(); ++r) {
+      const size_t s = rerun[r];
+      plen[s] = rr.plen[r];
+      h_same[s] = rr.same[r];
+      sstat[s] = rr.sstat[r];
+      parent_flags_out[s] = rr.parent_flag[r];
+      std::copy_n(&rr.parent_id[AG_SLICE_BLOCK_ID_BYTES * r], AG_SLICE_BLOCK_ID_BYTES,
+                  parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s);
+      data_offsets_out[s] = rr.data_offset[r];
+      data_lens_out[s] = rr.data_len[r];
+    }
   }
   std::vector<uint8_t> ok(n);
   pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
@@ -882,18 +973,27 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   const size_t n = nslices;
   int st;
   // Pass 0 decodes with ANY_K on the device (per-slice window patterns, no host per-slice work);
-  // a slice with surplus kept shreds that then fails some check could decode differently under
-  // the crate's decoder over every kept shred, so the batch is redone with EXACT (pass 1).  A
-  // slice that passes every check decoded the codeword its signed root commits, which every
-  // kept shred matches: EXACT agrees there.  The packets' lengths change only
-  // in step 7 (PETS / AONT serialize the absent datagrams before decrypting, into length-0 slots
-  // that a redo parses as absent), so the redo starts from the same datagrams.
+  // a slice with surplus kept shreds that then fails the padding or the Merkle check could decode
+  // differently under the crate's decoder over every kept shred, so those slices -- and only
+  // those -- are decoded again with EXACT in one batched pass (rerun_exact), as the Regular
+  // deshred does.  A slice that decoded and matches its signed root decoded the codeword that
+  // root commits, which every kept shred matches: EXACT agrees there, whatever
+  // its decryption or its parse then say.  The re-run slices were not among the slices whose
+  // absent datagrams PETS / AONT serialized, nor among the decrypted ones, and they still fail
+  // (rerun_exact), so their statuses follow from the coder's result and the root comparison.
+  // Pass 1, the whole batch with EXACT on the coder's host-pattern route, is what shred sizes
+  // and batches outside the device-pattern path run instead of pass 0 (!fast_ok).  The packets'
+  // lengths change only in step 7 (PETS / AONT serialize the absent datagrams before decrypting,
+  // into length-0 slots that a redo parses as absent), so a redo starts from the same datagrams.
+  c->last_rerun_slices = c->last_rerun_passes = 0;
   DeshredViews v;
-  std::vector<uint8_t> ok(n), pre_ok(n);
+  std::vector<uint8_t> ok(n), pre_ok(n), h_same(n), sstat(n);
+  std::vector<int64_t> plen(n);
+  std::vector<uint32_t> rerun;
   uint8_t* d_ok = nullptr;
   uint32_t* fresh = nullptr;
   const bool fast_ok = pipe_tail_ok(S, k.m, true) && n > 1 && k.m >= kDataShreds && k.m <= 2 * kDataShreds;
-  auto run_pass = [&](int pass, bool* redo) -> int {
+  auto run_pass = [&](int pass) -> int {
     // 1-3. the kept shreds of every slice (the Regular pipeline's steps with this shredder's data
     //      / coding layout), payloads parsed straight into their codeword rows
     if ((st = deshred_front(c, k, n, S, nullptr, packets, packet_stride, packet_lens, pk, codewords, nullptr, 0, 0, &v)))
@@ -903,13 +1003,14 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     //    codeword rows already), then decrypt_payload (PETS / AONT) after the raw shreds are
     //    taken.  Pass 0: ANY_K with the window patterns built on the device from the kept
     //    shreds' codeword-row words; pass 1: the crate's decoder over every kept shred (EXACT)
-    std::vector<int64_t> plen(n);
+    bool any_k = false;
     bool surplus = false;
     for (size_t s = 0; s < n; ++s) surplus |= __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
     bool full_data = false;
     if (kind == AG_SHREDDER_AONT)
       for (size_t s = 0; s < n; ++s) full_data |= (h_present[s] & 0xFFFFFFFFull) == 0xFFFFFFFFull;
     if (pass == 0 && pipe_tail_ok(S, k.m, !surplus && !full_data)) {
+      any_k = true;
       // codeword-row present words (pipe_coder_deshred: data | coding 0..31 << 32, coding
       // 32..63 in word 1 when m > 32); AONT's rows are the codeword rows
       const size_t wps = k.m > kDataShreds ? 2 : 1;
@@ -977,9 +1078,15 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     uint8_t* same;
     if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
     if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    std::vector<uint8_t> h_same(n);
     AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
     AG_HIP(hipStreamSynchronize(c->stream));
+    // the slices the ANY_K decode may have wronged (regular_deshred's step 6b)
+    rerun.clear();
+    for (size_t s = 0; any_k && s < n; ++s) {
+      const bool failed = plen[s] == -AG_RS_ERR_INVALID_PADDING || (plen[s] >= 0 && !h_same[s]);
+      if (failed && __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds))
+        rerun.push_back(static_cast<uint32_t>(s));
+    }
     if (k.aon >= 0) {
       // the absent datagrams of the slices that decoded and match their root, serialized from
       // the encrypted rows; then decrypt_payload (BadEncoding for a failed key check)
@@ -1014,22 +1121,44 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
         if (pre_ok[s]) plen[s] = pl[s];
     }
     // 6. SlicePayload::try_from on the (decrypted) payload
-    std::vector<uint8_t> sstat(n);
     if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
                                    parent_ids_out, data_offsets_out, data_lens_out)))
       return st;
     pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
                   is_last_out);
-    for (size_t s = 0; s < n; ++s)
-      *redo |= !ok[s] && __builtin_popcountll(h_present[s]) > static_cast<int>(kDataShreds);
     return AG_RS_OK;
   };
-  for (int pass = fast_ok ? 0 : 1; pass < 2; ++pass) {
-    bool redo = false;
-    // the side-stream rule for AONT's SHA-256, which a pass forks in step 4 and joins in step
-    // 5's decrypt: an error anywhere in a pass drains the side stream
-    if ((st = run_pass(pass, &redo))) return drain_side(c, st);
-    if (!redo) break;
+  // the side-stream rule for AONT's SHA-256, which a pass forks in step 4 and joins in step
+  // 5's decrypt: an error anywhere in a pass drains the side stream
+  if ((st = run_pass(fast_ok ? 0 : 1))) return drain_side(c, st);
+  if (!rerun.empty()) {
+    // 6b. the batched EXACT pass over the listed slices; their entries replace pass 0's
+    RerunResult rr;
+    bool passed = false;
+    if ((st = rerun_exact(c, k, rerun, S, nullptr, packets, packet_stride, v, codewords, cw_stride, &rr, &passed)))
+      return st;
+    if (passed) {
+      // A listed slice that decodes and matches its root after all (a SHA-256 collision, or two
+      // decoders of this library disagreeing) cannot be finished here as Regular finishes it:
+      // PETS / AONT would still have to serialize its absent datagrams from the encrypted rows
+      // and decrypt it, stages that run over the whole batch inside a pass and have run already.
+      // Correct before cheap: the batch is redone with EXACT, which does exactly that.
+      if ((st = run_pass(1))) return drain_side(c, st);
+    } else {
+      for (size_t r = 0; r < rerun.size(); ++r) {
+        const size_t s = rerun[r];
+        plen[s] = rr.plen[r];
+        h_same[s] = rr.same[r];
+        sstat[s] = rr.sstat[r];
+        parent_flags_out[s] = rr.parent_flag[r];
+        std::copy_n(&rr.parent_id[AG_SLICE_BLOCK_ID_BYTES * r], AG_SLICE_BLOCK_ID_BYTES,
+                    parent_ids_out + AG_SLICE_BLOCK_ID_BYTES * s);
+        data_offsets_out[s] = rr.data_offset[r];
+        data_lens_out[s] = rr.data_len[r];
+      }
+      pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out,
+                    slice_indices_out, is_last_out);
+    }
   }
   // 7. fill_missing_shreds: every absent slot of a successful slice gets its datagram (PETS /
   //    AONT serialized theirs from the encrypted rows, before the decrypt)

@@ -188,6 +188,7 @@ def load():
     sigs["ag_rs_internal_server_jobs"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_window_kernels"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_merkle_kernels"] = ([p, p], i)  # test aid, not in the header
+    sigs["ag_rs_internal_last_exact_rerun"] = ([p, p], i)  # test aid, not in the header
     for name, (args, res) in sigs.items():
         if not hasattr(L, name):  # older build (A/B timing of a previous commit); tests
             continue              # check the shipped library exports everything
@@ -763,6 +764,16 @@ def last_merkle_kernels(ctx: Context) -> set:
     out = ctypes.c_uint32(0)
     _check(load().ag_rs_internal_last_merkle_kernels(ctx.handle, ctypes.byref(out)), "last_merkle_kernels")
     return {name for i, name in enumerate(MERKLE_KERNELS) if out.value >> i & 1}
+
+
+def last_exact_rerun(ctx: Context) -> tuple:
+    """(slices, passes) of the last composed deshred call on ``ctx`` (test aid): the slices it
+    decoded again with the crate's decoder over every kept shred (failed the padding or Merkle
+    check with more than 32 kept shreds), and the batched EXACT coder passes it made for them
+    (one, whatever their number, sizes or shredder; none for an empty set)."""
+    out = (ctypes.c_uint64 * 2)()
+    _check(load().ag_rs_internal_last_exact_rerun(ctx.handle, out), "last_exact_rerun")
+    return int(out[0]), int(out[1])
 
 
 def merkle_verify_batch(ctx: Context, n: int, leaf_bytes: int, leaves, leaf_stride: int, index, roots,

@@ -18,6 +18,12 @@ the reference (oracle/shredder_oracle.py, checker only).
 --mixed-sizes times both sides over a block's mix of shred sizes (bench_coder.mixed_sizes):
 ag_shredder_shred_batch_var and ag_shredder_deshred_batch_var against loops of the uniform
 calls; see mixed_leg and mixed_deshred_leg.
+
+--adversarial-frac F (with --arrived 40): a fraction F of the slices comes from a leader that
+alters one shred after encoding and signs the tree over the altered shreds (byzantine_datagrams).
+Every such datagram validates, the slice fails the follower's ANY_K pass and, arriving with more
+than 32 datagrams, is decoded again with the crate's decoder over every kept shred: the line's
+rerun_slices / rerun_passes say how many slices that was and in how many batched passes.
 """
 from __future__ import annotations
 
@@ -35,6 +41,59 @@ PKT = 1344  # datagram slot (1325 bytes for a 1 KiB shred, rounded to 64)
 NAMES = {"regular": "RegularShredder", "coding_only": "CodingOnlyShredder", "pets": "PetsShredder",
          "aont": "AontShredder"}
 KINDS = {"regular": (0, 32, 0), "coding_only": (1, 64, 0), "pets": (2, 33, 16), "aont": (3, 32, 16)}
+
+
+def adversarial_slices(n, frac):
+    """The slices of a Byzantine leader: round(frac * n) of n, seeded, ascending (numpy)."""
+    import numpy as np
+
+    r = int(round(frac * n))
+    return np.sort(np.random.default_rng(0xB12A).permutation(n)[:r])
+
+
+def byzantine_datagrams(ctx, leaves, num_data, slots, sidx, last, seed, pk, pkt):
+    """The 64 datagrams per slice of a leader that signs shreds which are no codeword, built on
+    the device from the public calls.  leaves: [R][64][S], a copy of R slices' 64 output raw
+    shreds as the shred call left them; one shred of each is XORed with 0x5A, then
+    ag_merkle_build_batch, ag_slice_sign_batch and ag_shred_serialize_batch over the altered
+    shreds -> (datagrams [R * 64][pkt], lengths [R * 64])."""
+    import torch
+
+    from alpenglow_amd import rs
+
+    R, _, S = leaves.shape
+    dev = leaves.device
+    g = torch.Generator(device="cpu").manual_seed(0x7A3)
+    tamper = torch.randint(0, 64, (R,), generator=g).to(dev)
+    leaves[torch.arange(R, device=dev), tamper] ^= 0x5A
+    roots = torch.empty((R, 32), dtype=torch.uint8, device=dev)
+    proofs = torch.empty((R * 64, 192), dtype=torch.uint8, device=dev)
+    rs.merkle_build_batch(ctx, 64, S, R, leaves, S, 64 * S, roots, proofs=proofs, proofs_stride=64 * 192)
+    sigs = torch.empty((R, 64), dtype=torch.uint8, device=dev)
+    rs.slice_sign_batch(ctx, R, seed, pk, slots, sidx, last, roots, sigs)
+    j = torch.arange(64, device=dev).repeat(R)
+    cols = dict(kind=(j >= num_data).to(torch.uint8), slot=slots.repeat_interleave(64).contiguous(),
+                slice_index=sidx.repeat_interleave(64).contiguous(), is_last=last.repeat_interleave(64).contiguous(),
+                shred_index=j.to(torch.int32), data_len=torch.full((R * 64,), S, dtype=torch.int32, device=dev),
+                sig=sigs.repeat_interleave(64, dim=0).contiguous(),
+                height=torch.full((R * 64,), 6, dtype=torch.int32, device=dev))
+    c = rs.ShredColumns.of(cols["kind"], cols["slot"], cols["slice_index"], cols["is_last"], cols["shred_index"], leaves,
+                           S, cols["data_len"], cols["sig"], proofs, 192, cols["height"])
+    out = torch.zeros((R * 64, pkt), dtype=torch.uint8, device=dev)
+    lens = torch.zeros(R * 64, dtype=torch.int32, device=dev)
+    rs.shred_serialize_batch(ctx, R * 64, c, out, pkt, lens)
+    torch.cuda.synchronize()
+    return out, lens
+
+
+def last_rerun(ctx):
+    """(slices, passes) of the context's last composed deshred, or (None, None) on a library
+    built before the counters (an A/B against an older build)."""
+    from alpenglow_amd import rs
+
+    if not hasattr(rs.load(), "ag_rs_internal_last_exact_rerun"):
+        return None, None
+    return rs.last_exact_rerun(ctx)
 
 
 def mixed_leg(args):
@@ -128,7 +187,7 @@ def mixed_leg(args):
            for k, v in times.items()}
     var()  # the block's datagrams again (the uniform leg ran last)
     deshred = mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pkts, lens, timed,
-                                lambda: uniform(1024, d1024))
+                                lambda: uniform(1024, d1024), (slots.cpu().numpy(), sidx.cpu().numpy(), last.cpu().numpy()))
     print(json.dumps({
         "metric": "slices/s composed RegularShredder shred over a block's mix of shred sizes, one var call",
         "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "higher_is_better": True, "n_gpus": 1,
@@ -145,9 +204,9 @@ def mixed_leg(args):
     ctx.close()
 
 
-def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pkts, lens, timed, shred_1024):
+def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pkts, lens, timed, shred_1024, hdrs):
     """The follower's side of --mixed-sizes: the block mixed_leg shredded (pkts / lens hold
-    ag_shredder_shred_batch_var's datagrams), a random 32 of 64 datagrams per slice received,
+    ag_shredder_shred_batch_var's datagrams), a random --arrived (default 32) of 64 datagrams per slice received,
     legs interleaved step by step:
       var_mix        ag_shredder_deshred_batch_var, one call
       presorted_mix  the datagrams already regrouped by size, ag_shredder_deshred_batch once per
@@ -167,8 +226,22 @@ def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pk
 
     n, stride = args.slices, 64 * 1024
     g = torch.Generator(device="cpu").manual_seed(0xF011)
-    pick = torch.argsort(torch.rand((n, 64), generator=g), dim=1)[:, :32]
+    pick = torch.argsort(torch.rand((n, 64), generator=g), dim=1)[:, :args.arrived]
     keep = torch.zeros((n, 64), dtype=torch.bool).scatter_(1, pick, True).reshape(-1).to(dev)
+    # --adversarial-frac: the Byzantine leader's slices get their datagrams in place, size by size
+    adv = adversarial_slices(n, args.adversarial_frac)
+    bad = torch.zeros(n, dtype=torch.bool, device=dev)
+    if len(adv):
+        hdr = [torch.from_numpy(x).to(dev) for x in hdrs]
+        seed = torch.arange(32, dtype=torch.uint8).to(dev)
+        for S in np.unique(mix[adv]).tolist():
+            idx = torch.from_numpy(adv[mix[adv] == S]).to(dev)
+            leaves = cw.view(n, stride)[idx, :64 * S].reshape(len(idx), 64, S).contiguous()
+            bp, bl = byzantine_datagrams(ctx, leaves, 32, hdr[0][idx], hdr[1][idx], hdr[2][idx], seed, pk, PKT)
+            at = (idx[:, None] * 64 + torch.arange(64, device=dev)[None, :]).reshape(-1)
+            assert torch.equal(lens[at], bl)
+            pkts[at] = bp
+        bad[torch.from_numpy(adv).to(dev)] = True
     got = lens * keep  # the received lengths, var layout
     ord_t = torch.from_numpy(order).to(dev)
     rows = (ord_t[:, None] * 64 + torch.arange(64, device=dev)[None, :]).reshape(-1)  # datagram rows, sorted by size
@@ -211,18 +284,25 @@ def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pk
     legs = {"var_mix": (var, lambda: lens.copy_(got)), "presorted_mix": (per_size, lambda: slens.copy_(sgot)),
             "runs_mix": (runs, lambda: None), "uniform_1024": (uniform, lambda: lens_u.copy_(got_u))}
     res, times = {}, {k: [] for k in legs}
+    rerun = (None, None)
     for step in range(max(args.warmup, 2) + args.steps):
         for k, (f, reset) in legs.items():
             reset()
             out = []
             t = timed(lambda: out.extend(f()))
             res[k] = out
+            if k == "var_mix":
+                rerun = last_rerun(ctx)
             if step >= max(args.warmup, 2):
                 times[k].append(t)
-    ok = {k: all(bool((r.status == 0).all()) for r in v) for k, v in res.items()}
+    # every honest slice OK, every Byzantine one failed (var layout; the regrouped legs: sorted by size)
+    bad_h = bad.cpu().numpy()
+    fails = {"var_mix": bad_h, "presorted_mix": bad_h[order], "runs_mix": bad_h[order], "uniform_1024": np.zeros(n, bool)}
+    ok = {k: bool(np.array_equal(np.concatenate([np.asarray(r.status) for r in v]) != 0, fails[k])) for k, v in res.items()}
     r = res["var_mix"][0]
-    same = bool((r.data_offsets == 9).all()) and bool((r.data_lens == dmix).all())
-    dl = torch.from_numpy(dmix.astype(np.int64)).to(dev)
+    good = ~bad_h
+    same = bool((np.asarray(r.data_offsets)[good] == 9).all()) and bool((np.asarray(r.data_lens)[good] == dmix[good]).all())
+    dl = torch.from_numpy(np.where(good, dmix, 0).astype(np.int64)).to(dev)
     col = torch.arange(32 * 1024 - 10, device=dev)[None, :]
     cwv = cw.view(n, stride)
     for b in range(0, n, 4096):  # payload bytes against the input, a few thousand slices at a time
@@ -230,9 +310,12 @@ def mixed_deshred_leg(args, ctx, dev, mix, dmix, order, starts, data, pk, cw, pk
         same = same and bool(((cwv[b:e, 9:9 + col.shape[1]] == data[b:e, :col.shape[1]]) | (col >= dl[b:e, None])).all())
     out = {k: {"wall_ms": statistics.median(v), "slices_per_s": n / (statistics.median(v) * 1e-3), "steps": len(v)}
            for k, v in times.items()}
-    return {"metric": "slices/s composed RegularShredder deshred over a block's mix of shred sizes from a random 32 "
+    return {"metric": "slices/s composed RegularShredder deshred over a block's mix of shred sizes from a random "
+                      f"{args.arrived} "
                       "of 64 datagrams per slice, one var call",
             "value": out["var_mix"]["slices_per_s"], "unit": "slices/s", "legs": out,
+            "arrived": args.arrived, "adversarial_frac": args.adversarial_frac, "adversarial_slices": int(len(adv)),
+            "rerun_slices": rerun[0], "rerun_passes": rerun[1],
             "ratios": {"var_mix_over_runs_mix": out["runs_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
                        "var_mix_over_presorted_mix": out["presorted_mix"]["wall_ms"] / out["var_mix"]["wall_ms"],
                        "var_mix_over_uniform_1024": out["uniform_1024"]["wall_ms"] / out["var_mix"]["wall_ms"]},
@@ -250,6 +333,8 @@ def main():
                     help="shred size S (even, <= 1024): payloads of 32 S - 1 bytes; 1024 = maximum slices")
     ap.add_argument("--kind", choices=list(KINDS), default="regular",
                     help="the shredder (shredder.rs:336-500); the CPU baseline is timed for regular only")
+    ap.add_argument("--adversarial-frac", type=float, default=0.0,
+                    help="fraction of the slices from a leader that signs altered shreds (use with --arrived 40)")
     ap.add_argument("--mixed-sizes", action="store_true",
                     help="time ag_shredder_shred_batch_var on a block's mix of shred sizes against the uniform call")
     args = ap.parse_args()
@@ -308,8 +393,28 @@ def main():
     torch.cuda.synchronize()
     full_lens = lens.clone()
     full_pkts = pkts[: 64 * 8].clone()
-    for _ in range(args.warmup):
+    # --adversarial-frac: the Byzantine leader's datagrams, built once from the shredded codewords
+    # and put into their slots after every shred call
+    adv = adversarial_slices(n, args.adversarial_frac)
+    bad = torch.zeros(n, dtype=torch.bool, device=dev)
+    if len(adv):
+        idx = torch.from_numpy(adv).to(dev)
+        out_rows = [r for r in range(32 + m) if (kind != 1 or r >= 32) and (kind != 2 or r != 31)][:64]
+        leaves = cw.view(n, 32 + m, S)[idx][:, out_rows].contiguous()
+        adv_pkts, adv_lens = byzantine_datagrams(ctx, leaves, {0: 32, 1: 0, 2: 31, 3: 32}[kind], slots[idx], sidx[idx],
+                                                 last[idx], seed, pk, PKT)
+        adv_at = (idx[:, None] * 64 + torch.arange(64, device=dev)[None, :]).reshape(-1)
+        assert torch.equal(full_lens[adv_at], adv_lens)
+        bad[idx] = True
+
+    def arrive():
+        """The datagrams that did not arrive dropped, the Byzantine leader's slices in place."""
         lens.mul_(keep)
+        if len(adv):
+            pkts[adv_at] = adv_pkts
+
+    for _ in range(args.warmup):
+        arrive()
         deshred()
         shred()
     torch.cuda.synchronize()
@@ -319,28 +424,36 @@ def main():
         shred()
         torch.cuda.synchronize()
         b = time.perf_counter()
-        lens.mul_(keep)  # the datagrams that did not arrive
+        arrive()
         torch.cuda.synchronize()
         c = time.perf_counter()
         res = deshred()  # synchronous
         d = time.perf_counter()
         t_sh += b - a
         t_de += d - c
-    ok = bool((res.status == 0).all()) and bool(torch.equal(lens, full_lens)) and \
-        bool(torch.equal(pkts[: 64 * 8], full_pkts)) and bool((res.data_lens == D).all())
-    off = res.data_offsets[:64].tolist()
-    ok = ok and all(torch.equal(cw[b, off[b]:off[b] + D], data[b, :D]) for b in range(64))
+    rerun = last_rerun(ctx)
+    # every honest slice restored, every Byzantine one failed with its datagram lengths as received
+    bad_h = bad.cpu().numpy()
+    good = torch.from_numpy(~bad_h).to(dev)
+    ok = bool(np.array_equal(np.asarray(res.status) != 0, bad_h)) and \
+        bool(torch.equal(lens.view(n, 64)[good], full_lens.view(n, 64)[good])) and \
+        bool((np.asarray(res.data_lens)[~bad_h] == D).all())
+    if len(adv):
+        ok = ok and bool(torch.equal(lens.view(n, 64)[bad], (full_lens * keep).view(n, 64)[bad]))
+    first = [b for b in range(n) if not bad_h[b]][:64]  # the spot checks' slices: honest ones
+    head = [b for b in first if b < 8]
+    ok = ok and bool(torch.equal(pkts.view(n, 64, PKT)[head], full_pkts.view(8, 64, PKT)[head]))
+    off = res.data_offsets.tolist()
+    ok = ok and all(torch.equal(cw[b, off[b]:off[b] + D], data[b, :D]) for b in first)
     # spot check: two slices against the CPU composition of the reference (checker only)
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import shredder_oracle as so
-    hp, hl = pkts[:128].cpu().numpy(), lens[:128].cpu().numpy()
-    hk = keys[:32].cpu().numpy().tobytes()
-    sl, si, ls = slots[:2].cpu().tolist(), sidx[:2].cpu().tolist(), last[:2].cpu().tolist()
     spot = True
-    for b in range(2):
-        want, *_ = so.shred_kind(kind, None, data[b, :D].cpu().numpy().tobytes(), sl[b], si[b], bool(ls[b]),
-                                 bytes(range(32)), hk[16 * b:16 * b + 16])
-        spot &= all(hp[b * 64 + j, :hl[b * 64 + j]].tobytes() == want[j] for j in range(64))
+    for b in first[:2]:
+        hp, hl = pkts[64 * b:64 * b + 64].cpu().numpy(), lens[64 * b:64 * b + 64].cpu().numpy()
+        want, *_ = so.shred_kind(kind, None, data[b, :D].cpu().numpy().tobytes(), int(slots[b]), int(sidx[b]),
+                                 bool(last[b]), bytes(range(32)), keys[16 * b:16 * b + 16].cpu().numpy().tobytes())
+        spot &= all(hp[j, :hl[j]].tobytes() == want[j] for j in range(64))
     steps = args.steps
     line = {
         "metric": f"slices/s composed {NAMES[args.kind]} shred + deshred (datagrams in, datagrams out), "
@@ -358,6 +471,11 @@ def main():
         "data": "synthetic (splitmix64 payloads, device-generated; one leader key)",
         "config": {"workload": f"{n} slices x {D + 9} B payload, 64 datagrams of {S + 301} B per slice; deshred from a "
                                f"random {args.arrived} of 64 datagrams per slice"},
+        "arrived": args.arrived,
+        "adversarial_frac": args.adversarial_frac,
+        "adversarial_slices": int(len(adv)),
+        "rerun_slices": rerun[0],
+        "rerun_passes": rerun[1],
         "payload_GiBps": n * (D + 9) * steps / (t_sh + t_de) / GIB,
         "calls_ms": {"shred_batch": t_sh * 1e3 / steps, "deshred_batch": t_de * 1e3 / steps},
         "shred_slices_per_s": n * steps / t_sh,

@@ -579,9 +579,12 @@ int ag_shredder_shred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint8_t* p
  * comes from the caller: a follower knows S_s from any stored datagram of the slice, its length
  * minus ag_shred_datagram_bytes(0, 6).  For every slice, every output (status, header, parent,
  * data offset and length, the codeword bytes, the datagram slots, packet_lens) is what
- * ag_shredder_deshred_batch gives when run on that slice alone with S = S_s; the number of
- * launches does not depend on the mix of sizes (but for the one-by-one EXACT re-run of failed
- * slices with surplus shreds).  A datagram in a slot of slice s whose data length is not S_s
+ * ag_shredder_deshred_batch gives when run on that slice alone with S = S_s -- but for the rows
+ * of the absent coding shreds of a slice that fails its padding check with exactly 32 kept
+ * shreds, which are unspecified in both calls (written or left as they were); the number of
+ * launches does not depend on the mix of sizes, nor on how many slices fail: the failed slices
+ * with surplus shreds (a Byzantine leader's) are decoded again with EXACT in one batched pass over
+ * all of them, whatever their sizes.  A datagram in a slot of slice s whose data length is not S_s
  * counts as absent, so a slice given the wrong S_s ends as NOT_ENOUGH_SHARDS, never as a
  * whole-call error.  No byte of a slice's codeword stride past 64 * S_s is written, no byte of
  * a datagram slot past the length written there, and no present datagram; absent slots of
@@ -613,8 +616,9 @@ int ag_shredder_deshred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint32_t
  * AONT only): the key cipher::encrypt_with_random_key drew (crypto/cipher.rs) -- the caller
  * supplies it, so the output is reproducible.  MAX_DATA_SIZE is 16 bytes less for PETS / AONT
  * (TooMuchData).  The deshred side gives the verdicts of the crate's decoder over every kept
- * shred (EXACT: a batch decodes ANY_K on the device and is redone with EXACT when a slice with
- * surplus shreds fails), decrypts after the raw shreds are taken (decrypt_payload: BadEncoding
+ * shred (EXACT: a batch decodes ANY_K on the device, and the slices that then fail the padding
+ * or the Merkle check with surplus shreds -- only those -- are decoded again with EXACT in one
+ * batched pass), decrypts after the raw shreds are taken (decrypt_payload: BadEncoding
  * for a buffer shorter than the key or a failed key check, :512-528), then check_merkle_tree,
  * SlicePayload::try_from and fill_missing_shreds as ag_shredder_deshred_batch; the parsed data
  * is at codewords + s * codeword_stride + data_offsets_out[s].  The datagrams are parsed into
