@@ -25,7 +25,13 @@
 namespace ag {
 namespace ed {
 
+// AG_ED_NO_FORCE_INLINE (host check builds under a sanitizer only; the library and the kernels
+// never define it): plain inline, so the instrumented verify compiles function by function.
+#ifdef AG_ED_NO_FORCE_INLINE
+#define ED_INL __host__ __device__ inline
+#else
 #define ED_INL __host__ __device__ inline __attribute__((always_inline))
+#endif
 
 struct Fe {
   int32_t v[10];

@@ -4,7 +4,13 @@
 // (hex, MSG may be "-" for empty); stdout: one hex / 0 / 1 line each.  "bench_verify PK MSG
 // SIG N" times N verifications on one host thread (bench_sig.py's native CPU baseline leg)
 // and prints verifications per second.
+//
+// Field ops on explicit limb vectors (ten signed decimal integers per operand, limb i at bit
+// kOff[i]): "fe_mul F G" | "fe_sq F" | "fe_sq2 F" | "fe_invert F" print the result's ten limbs
+// as one comma-separated token; "fe_to_words F" prints the canonical value's 32 bytes (hex).
+// They reach limb patterns at the header's bound rule, which no signature is known to produce.
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <iostream>
 #include <sstream>
@@ -31,6 +37,18 @@ static std::string hex(const uint8_t* p, size_t n) {
   return s;
 }
 
+static bool read_fe(std::istringstream& is, Fe& f) {
+  for (int i = 0; i < 10; ++i) {
+    long long v;
+    if (!(is >> v) || v < INT32_MIN || v > INT32_MAX) return false;
+    f.v[i] = static_cast<int32_t>(v);
+  }
+  return true;
+}
+static void print_fe(const Fe& f) {
+  for (int i = 0; i < 10; ++i) std::cout << f.v[i] << (i < 9 ? "," : "\n");
+}
+
 int main() {
   std::vector<int32_t> table(64 * 8 * 30);
   for (int r = 0; r < 64; ++r) base_table_row(r, table.data());
@@ -38,7 +56,28 @@ int main() {
   while (std::getline(std::cin, line)) {
     std::istringstream is(line);
     std::string op, a, b, c;
-    is >> op >> a >> b >> c;
+    is >> op;
+    if (op.rfind("fe_", 0) == 0) {
+      Fe f, g, o;
+      if (!read_fe(is, f) || (op == "fe_mul" && !read_fe(is, g))) {
+        std::cout << "bad\n";
+      } else if (op == "fe_to_words") {
+        uint32_t w[8];
+        uint8_t bytes[32];
+        fe_to_words(f, w);
+        store_words(bytes, w);
+        std::cout << hex(bytes, 32) << "\n";
+      } else {
+        if (op == "fe_mul") fe_mul(o, f, g);
+        else if (op == "fe_sq") fe_sq(o, f);
+        else if (op == "fe_sq2") fe_sq2(o, f);
+        else if (op == "fe_invert") fe_invert(o, f);
+        else o = fe_zero();
+        print_fe(o);
+      }
+      continue;
+    }
+    is >> a >> b >> c;
     if (op == "pk") {
       auto seed = unhex(a);
       uint8_t pk[32];

@@ -16,7 +16,7 @@ import pytest
 
 import ed25519_oracle as eo
 import merkle_oracle as mo
-from ed_cases import le, verify_cases
+from ed_cases import SHA512_EDGE_LENS, check_fe_output, edge_lines, edge_messages, fe_cases, flip_last, le, verify_cases
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "ed25519_rfc8032.json")
@@ -130,6 +130,24 @@ def test_host_core_verify_cases(hostchk):
     assert "1" in want and "0" in want
 
 
+def test_host_core_sha512_boundary_lengths(hostchk):
+    """Sign and verify at every message length where either SHA-512 (challenge over R || A || M,
+    nonce over prefix || M) changes its padding rule (ed_cases.SHA512_EDGE_LENS); the message
+    with its last byte flipped is rejected."""
+    lines, want = edge_lines()
+    assert hostchk(lines) == want
+
+
+def test_host_core_field_ops_vs_python_integers(hostchk):
+    """fe_mul / fe_sq / fe_sq2 / fe_invert / fe_to_words on explicit limb vectors against Python
+    integers mod 2^255 - 19: canonical edge values, 50 seeded random ones, and limb vectors at
+    the header's bound rule (g at 3x a reduced element, f at 20x, squares at 3x) in all-plus,
+    all-minus and alternating signs (ed_cases.fe_cases; tests/test_sanitizers.py runs the same
+    lines under UBSan, where a breach of the rule is a reported signed overflow)."""
+    cases = fe_cases()
+    check_fe_output(cases, hostchk([line for line, _ in cases]))
+
+
 # ---- device batches (GPU) ----------------------------------------------------------------
 
 def _dev(b: bytes):
@@ -229,6 +247,60 @@ def test_gpu_verify_shared_key_large_batch(ctx):
     assert pkb == eo.secret_to_public(sk)
     for t in (0, 1, 97, 1000, n - 1):
         assert eo.verify(pkb, mh[t].tobytes(), sh[t].tobytes()) == bool(want[t])
+
+
+@pytest.mark.gpu
+def test_gpu_sign_verify_sha512_boundary_lengths(ctx):
+    """Device sign and verify at every message length where the challenge hash (64 + len) or the
+    nonce hash (32 + len) changes its SHA-512 padding rule: four seeds per length, messages at an
+    odd stride larger than the length.  Signatures equal the oracle's; one verify batch over all
+    lengths accepts them all, a second with each last message byte flipped rejects, and a third
+    with msg_lens one short rejects too: the length, not the stride, bounds the hash."""
+    import torch
+    from alpenglow_amd import rs
+    per = 4
+    items = edge_messages(seeds_per_len=per)
+    stride = max(SHA512_EDGE_LENS) + 2
+    assert stride % 2 == 1
+    n = len(items)
+    pks_b, sigs_b = [eo.secret_to_public(sk) for sk, _ in items], [eo.sign(sk, m) for sk, m in items]
+    seeds, pks = _cat([sk for sk, _ in items]), _cat(pks_b)
+    got_sigs = []
+    for q, mlen in enumerate(SHA512_EDGE_LENS):    # one message length per sign call
+        st = mlen + 1 + mlen % 2                   # odd, larger than the length
+        buf = bytearray(b"\xEE" * (st * per))
+        for r in range(per):
+            buf[st * r:st * r + mlen] = items[per * q + r][1]
+        sig = _dev(bytes(64 * per))
+        rs.ed25519_sign_batch(ctx, per, seeds[32 * per * q:], 32, pks[32 * per * q:], 32, _dev(bytes(buf)), st, mlen, sig)
+        got_sigs.append(sig)
+    ctx.synchronize()
+    got = b"".join(g.cpu().numpy().tobytes() for g in got_sigs)
+    for t in range(n):
+        assert got[64 * t:64 * t + 64] == sigs_b[t], (t, len(items[t][1]))
+
+    def batch(msgs, lens):
+        rows = bytearray(b"\xEE" * (stride * n))
+        for t, m in enumerate(msgs):
+            rows[stride * t:stride * t + len(m)] = m
+        ok = torch.full((n,), 7, dtype=torch.uint8, device="cuda:0")
+        rs.ed25519_verify_batch(ctx, n, pks, 32, _dev(bytes(rows)), stride, _cat(sigs_b), 64, ok,
+                                msg_lens=torch.tensor(lens, dtype=torch.int32, device="cuda:0"))
+        ctx.synchronize()
+        return ok.cpu().numpy().tolist()
+
+    msgs = [m for _, m in items]
+    lens = [len(m) for m in msgs]
+    assert batch(msgs, lens) == [1 if eo.verify(pk, m, s) else 0 for pk, m, s in zip(pks_b, msgs, sigs_b)] == [1] * n
+    some = [t for t in range(n) if lens[t] >= 1]
+    flipped = [flip_last(m) if m else m for m in msgs]
+    got = batch(flipped, lens)
+    assert [got[t] for t in some] == [1 if eo.verify(pks_b[t], flipped[t], sigs_b[t]) else 0 for t in some]
+    assert not any(got[t] for t in some) and all(got[t] == 1 for t in range(n) if lens[t] == 0)
+    short = [max(0, x - 1) for x in lens]
+    got = batch(msgs, short)                       # the rows still hold the whole messages
+    assert [got[t] for t in some] == [1 if eo.verify(pks_b[t], msgs[t][:-1], sigs_b[t]) else 0 for t in some]
+    assert not any(got[t] for t in some)
 
 
 def _make_slice(rng, sk, slot, slice_index, is_last, shred_bytes=1024, n_leaves=64):

@@ -1,7 +1,7 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer builds of the host-only code (CPU, no GPU).
 
 The reference runs ASan / LSan / TSan weekly (/root/reference/.github/workflows/sanitizers.yml);
-SURVEY.md §5 asks for the same on this build's host C/C++.  Three programs, each compiled with
+SURVEY.md §5 asks for the same on this build's host C/C++.  Four programs, each compiled with
 -fsanitize=address,undefined -fno-sanitize-recover=all (leak detection on) and run here:
 
 * tests/native/patterns_selfcheck.cpp + alpenglow_amd/csrc/rs_patterns.cpp + gf16.cpp: the
@@ -10,9 +10,14 @@ SURVEY.md §5 asks for the same on this build's host C/C++.  Three programs, eac
 * alpenglow_amd/csrc/gen_consts.cpp + gf16.cpp: the constant generator (one restart: its
   tables must equal the committed rs_consts.inc's, and it self-checks every program);
 * tests/native/oracle_selfcheck.c + oracle/rs_oracle.c + oracle/rs_cpu_avx2.c: the C oracle and
-  the restated Avx2 engine (encode agreement, decode round trips, threaded block entry points).
+  the restated Avx2 engine (encode agreement, decode round trips, threaded block entry points);
+* tests/native/ed_host_check.cpp over alpenglow_amd/csrc/ed25519_core.hpp: the kernels' Ed25519
+  arithmetic as a stand-alone host program (never loaded into Python), built with
+  AG_ED_NO_FORCE_INLINE: with the header's forced inlining the instrumented verify is one
+  function that does not compile in ten minutes; without it the build takes seconds.
 """
 
+import json
 import os
 import shutil
 import subprocess
@@ -69,3 +74,36 @@ def test_oracle_asan_ubsan():
     _build(["gcc", "-std=c11", *SAN, "-pthread", os.path.join(NATIVE, "oracle_selfcheck.c"),
             os.path.join(ROOT, "oracle", "rs_oracle.c"), os.path.join(ROOT, "oracle", "rs_cpu_avx2.c"), "-o", exe])
     assert _run(exe).strip() == "ok"
+
+
+def test_ed25519_core_asan_ubsan():
+    """The 25.5-bit field arithmetic rests on a bound rule kept by hand (ed25519_core.hpp: g at
+    most 3x a reduced element, f * g at most ~60x); a breach is signed overflow.  Under the
+    sanitizers: the verify cases, sign / verify at the SHA-512 padding boundaries, the RFC 8032
+    vectors, and the field ops on limb vectors at the rule's bounds.  Exit status 0 (no report)
+    and every answer equal to the oracle's."""
+    import ed25519_oracle as eo
+    from ed_cases import check_fe_output, edge_lines, fe_cases, verify_cases
+
+    exe = os.path.join(BUILD, "ed_host_check_san")
+    _build(["hipcc", "--offload-host-only", "-std=c++20", *SAN, "-DAG_ED_NO_FORCE_INLINE", f"-I{CSRC}",
+            os.path.join(NATIVE, "ed_host_check.cpp"), "-o", exe])
+    hx = lambda b: b.hex() if b else "-"  # noqa: E731
+    cases = verify_cases(n_random=12)
+    lines = [f"verify {pk.hex()} {hx(m)} {sig.hex()}" for pk, m, sig in cases]
+    want = ["1" if eo.verify(pk, m, sig) else "0" for pk, m, sig in cases]
+    edge, edge_want = edge_lines()
+    lines += edge
+    want += edge_want
+    with open(os.path.join(ROOT, "tests", "golden", "ed25519_rfc8032.json")) as f:
+        for v in json.load(f)["vectors"]:
+            lines += [f"pk {v['secret']}", f"sign {v['secret']} {v['message'] or '-'}",
+                      f"verify {v['public']} {v['message'] or '-'} {v['signature']}"]
+            want += [v["public"], v["signature"], "1"]
+    fe = fe_cases()
+    lines += [line for line, _ in fe]
+    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=300, env=ENV)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    out = r.stdout.split()
+    assert out[:len(want)] == want
+    check_fe_output(fe, out[len(want):])
