@@ -1,13 +1,16 @@
 // The device context behind the C ABI (include/alpenglow_rs.h) and the helpers the host
-// translation units share: rs_api.cpp (the C ABI), rs_dispatch.cpp (the batch encode / decode
-// dispatch) and shredder_api.cpp.  Internal: not installed, included only by the host .cpp
-// files; nothing here is exported from the shared object.
+// translation units share: rs_api.cpp, rs_coder_api.cpp, crypto_api.cpp and wire_api.cpp (the C
+// ABI), rs_dispatch.cpp (the batch encode / decode dispatch) and shredder_api.cpp.  Internal: not
+// installed, included only by the host .cpp files; nothing here is exported from the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <chrono>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/alpenglow_rs.h"
@@ -23,17 +26,24 @@
 namespace ag {
 namespace host __attribute__((visibility("hidden"))) {
 
-// Grow-only device buffer.
+// Grow-only device buffer.  Owns its memory: move-only, freed on destruction.
 struct DevBuf {
   void* ptr = nullptr;
   size_t size = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : ptr(std::exchange(o.ptr, nullptr)), size(std::exchange(o.size, 0)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept {  // (declaring the moves deletes the copies)
+    if (this != &o) release();
+    ptr = std::exchange(o.ptr, nullptr);
+    size = std::exchange(o.size, 0);
+    return *this;
+  }
+  ~DevBuf() { release(); }
   int ensure(size_t n, hipStream_t stream) {
     if (n <= size) return AG_RS_OK;
     if (ptr) {
       if (hipStreamSynchronize(stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-      (void)hipFree(ptr);
-      ptr = nullptr;
-      size = 0;
+      release();
     }
     if (hipMalloc(&ptr, n) != hipSuccess) return AG_RS_ERR_OUT_OF_MEMORY;
     size = n;
@@ -49,13 +59,25 @@ struct DevBuf {
     size = 0;
   }
 };
+static_assert(!std::is_copy_constructible_v<DevBuf> && !std::is_copy_assignable_v<DevBuf>);
 
 // Grow-only pinned host buffer, mapped and coherent (fine-grained: never cached in the GPU's
 // L2, so one call's kernels cannot read another call's stale bytes): the crate-API
-// single-call kernels read and write it directly (zero-copy).
+// single-call kernels read and write it directly (zero-copy).  Owns its memory like DevBuf.
 struct PinBuf {
   void* ptr = nullptr;
   size_t size = 0;
+  void* dptr = nullptr;
+  PinBuf() = default;
+  PinBuf(PinBuf&& o) noexcept { *this = std::move(o); }
+  PinBuf& operator=(PinBuf&& o) noexcept {
+    if (this != &o) release();
+    ptr = std::exchange(o.ptr, nullptr);
+    size = std::exchange(o.size, 0);
+    dptr = std::exchange(o.dptr, nullptr);
+    return *this;
+  }
+  ~PinBuf() { release(); }
   int ensure(size_t n) {
     if (n <= size) return AG_RS_OK;
     release();
@@ -78,13 +100,18 @@ struct PinBuf {
   T* dev() const {  // the same bytes as the device addresses them (zero-copy over PCIe)
     return static_cast<T*>(dptr);
   }
-  void* dptr = nullptr;
   void release() {
     if (ptr) (void)hipHostFree(ptr);
+    leak();
+  }
+  // Forgets the memory without freeing it: for staging that a device kernel which never quit
+  // may still write (ag_rs_ctx::server_stop).
+  void leak() {
     ptr = dptr = nullptr;
     size = 0;
   }
 };
+static_assert(!std::is_copy_constructible_v<PinBuf> && !std::is_copy_assignable_v<PinBuf>);
 
 // "Upload only when the pattern set changed": a device buffer and the host key of what it
 // holds.  While the key matches (steady-state batches) a call neither copies nor waits.
@@ -116,11 +143,48 @@ struct UploadCache {
   }
 };
 
+// "Fill on the host, upload behind the queued work": pinned staging, the device buffer it is
+// copied to, and the event recorded after the copy.  No stream synchronisation: the staging may
+// be rewritten only once its last upload has completed, so host() waits for that event; a caller
+// that returns between host() and send() has uploaded nothing and leaves the event as it was.
+struct StagedUpload {
+  PinBuf pin;
+  DevBuf dev;
+  hipEvent_t ev = nullptr;  // recorded after the last upload
+  ~StagedUpload() {  // (the members free after it: once the last upload has read the staging)
+    if (!ev) return;
+    (void)hipEventSynchronize(ev);
+    (void)hipEventDestroy(ev);
+  }
+  // *out: `bytes` of staging for the caller to fill.  `dev` is not touched: growing it may
+  // synchronise the stream, which a caller that ends up uploading nothing must not pay for.
+  template <typename T>
+  int host(size_t bytes, T** out) {
+    if (ev) AG_HIP(hipEventSynchronize(ev));
+    else AG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    const int st = pin.ensure(bytes);
+    *out = pin.as<T>();
+    return st;
+  }
+  // The first `bytes` of the staging to `dst` on the stream, or to `dev`, grown to hold them.
+  int send(size_t bytes, hipStream_t stream, void* dst = nullptr) {
+    if (!dst) {
+      const int st = dev.ensure(bytes, stream);
+      if (st) return st;
+      dst = dev.ptr;
+    }
+    AG_HIP(hipMemcpyAsync(dst, pin.ptr, bytes, hipMemcpyHostToDevice, stream));
+    AG_HIP(hipEventRecord(ev, stream));
+    return AG_RS_OK;
+  }
+};
+
 }  // namespace host
 }  // namespace ag
 
 using ag::host::DevBuf;
 using ag::host::PinBuf;
+using ag::host::StagedUpload;
 using ag::host::UploadCache;
 
 struct ag_rs_ctx {
@@ -153,31 +217,23 @@ struct ag_rs_ctx {
   DevBuf d_empty_roots;                     // Merkle EMPTY_ROOTS [32][8] words
   DevBuf d_merkle_nodes;                    // Merkle node scratch (callers without a nodes buffer)
   uint32_t last_merkle_kernels = 0;         // MerkleLeafKernelBit of the last Merkle build's leaf kernel
-  DevBuf d_leaf_sizes;                      // ag_merkle_build_batch_var: leaf size per slice
-  PinBuf h_leaf_sizes;                      // its pinned host staging
-  hipEvent_t leaf_sizes_ev = nullptr;       // recorded after its upload
-  DevBuf d_block_meta;                      // block trees: first[nblocks] (u64), then count[nblocks] (u32)
-  PinBuf h_block_meta;                      // its pinned host staging
-  hipEvent_t block_meta_ev = nullptr;       // recorded after its upload
+  StagedUpload leaf_sizes;                  // ag_merkle_build_batch_var: leaf size per slice
+  StagedUpload block_meta;                  // block trees: first[nblocks] (u64), then count[nblocks] (u32)
   DevBuf d_aon_lens, d_aon_digests, d_aon_keys;  // all-or-nothing transforms
   DevBuf d_aon_lens2;                            // the side stream's SHA-256 lengths (AONT deshred)
   hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
   hipEvent_t side_fork = nullptr, side_join = nullptr;
   DevBuf d_slice_meta;                           // slice framing / parsing metadata
   DevBuf stage_pad;                              // restrided shards (sizes not whole 64-byte chunks)
-  DevBuf d_lens, d_strip;                   // coder batches: payload lengths, strip results
+  StagedUpload lens;                        // coder shred batches: payload lengths (var: | sizes | column prefix)
+  DevBuf d_strip;                           // coder batches: strip results
   DevBuf d_reenc_mask;                      // uniform coder deshreds: the re-encode's store mask word
   DevBuf d_pipe_few, d_pipe_mask;           // composed deshred: too-few flags, re-encode store masks
-  DevBuf d_present;                         // coder batches: per-slice present masks
-  PinBuf h_present;                         // their pinned host staging
-  hipEvent_t present_ev = nullptr;          // recorded after its upload
-  PinBuf h_lens;                            // coder shred batches: pinned staging of the lengths
-  hipEvent_t lens_ev = nullptr;             // recorded after its upload
+  StagedUpload present;                     // coder batches: per-slice present masks
   PinBuf h_strip;                           // coder deshred batches: pinned staging of the results
   PinBuf h_slice_meta;                      // slice parse batches: pinned staging of the results
   PinBuf h_pipe_meta;                       // composed deshreds: pinned staging of the per-slice columns
-  PinBuf h_rerun;                           // their EXACT re-run: pinned staging of the list | sizes | column prefix
-  hipEvent_t rerun_ev = nullptr;            // recorded after its upload
+  StagedUpload rerun;                       // their EXACT re-run: list | sizes | column prefix (sent into pipe scratch)
   uint64_t last_rerun_slices = 0, last_rerun_passes = 0;  // the last composed deshred's EXACT re-run (test aid)
   DevBuf d_ed_base;                         // Ed25519 fixed-base table (ed25519.hpp)
   static constexpr int kPipeBufs = 37;
@@ -282,11 +338,11 @@ struct ag_rs_ctx {
       // so those stay allocated
       mb = mb_dev = nullptr;
       server_stream = nullptr;
+      for (PinBuf& b : abandoned_pins) b.leak();
       abandoned_pins.clear();
       return;
     }
     (void)hipStreamSynchronize(server_stream);  // the server has exited (quit or idle timeout)
-    for (PinBuf& b : abandoned_pins) b.release();
     abandoned_pins.clear();
     (void)hipStreamDestroy(server_stream);
     (void)hipHostFree(mb);
@@ -294,67 +350,72 @@ struct ag_rs_ctx {
     server_stream = nullptr;
   }
 
+  // The buffers free themselves, after this body: it drains every stream first, so no queued
+  // work or pending upload can touch a member when its destructor runs.
   ~ag_rs_ctx() {
+    (void)hipSetDevice(device);
     server_stop();
     if (side) {
-      (void)hipSetDevice(device);
       (void)hipStreamSynchronize(side);
       (void)hipEventDestroy(side_fork);
       (void)hipEventDestroy(side_join);
       (void)hipStreamDestroy(side);
     }
-    if (own_stream) {
-      (void)hipSetDevice(device);
-      (void)hipStreamSynchronize(own_stream);
-    }
+    if (own_stream) (void)hipStreamSynchronize(own_stream);
     if (h2d) {
       (void)hipStreamSynchronize(h2d);
       (void)hipStreamSynchronize(d2h);
-      for (Slot& s : slot) {
-        s.in.release();
-        s.out.release();
+      for (Slot& s : slot)
         for (hipEvent_t e : {s.up, s.done, s.down})
           if (e) (void)hipEventDestroy(e);
-      }
       (void)hipStreamDestroy(h2d);
       (void)hipStreamDestroy(d2h);
     }
-    for (DevBuf* b : {&d_exp, &d_log, &d_skew, &d_log_walsh, &scratch, &d_flags, &d_loc, &d_blocks, &mask.dev,
-                      &stage_mask.dev, &xmask.dev, &d_rows, &d_xblocks, &x128.dev, &d_rows128, &syn.dev, &d_synblocks,
-                      &corr.dev, &d_corrk, &d_corrblocks, &d_empty_roots, &d_merkle_nodes, &d_aon_lens, &d_aon_digests, &d_aon_keys, &d_aon_lens2, &d_lens, &d_strip, &d_reenc_mask, &d_ed_base, &d_sh_roots, &d_sh_commit, &d_sh_onvalid, &d_sh_list, &stage_pad, &d_slice_meta, &one_in,
-                      &one_out, &d_pipe_few, &d_pipe_mask, &d_present, &d_block_meta, &d_leaf_sizes})
-      b->release();
-    for (DevBuf& b : pipe) b.release();
-    if (present_ev) {
-      (void)hipEventSynchronize(present_ev);
-      (void)hipEventDestroy(present_ev);
-    }
-    h_present.release();
-    if (lens_ev) {
-      (void)hipEventSynchronize(lens_ev);
-      (void)hipEventDestroy(lens_ev);
-    }
-    h_lens.release();
-    if (block_meta_ev) {
-      (void)hipEventSynchronize(block_meta_ev);
-      (void)hipEventDestroy(block_meta_ev);
-    }
-    h_block_meta.release();
-    if (leaf_sizes_ev) {
-      (void)hipEventSynchronize(leaf_sizes_ev);
-      (void)hipEventDestroy(leaf_sizes_ev);
-    }
-    h_leaf_sizes.release();
-    h_strip.release();
-    h_slice_meta.release();
-    h_pipe_meta.release();
-    if (rerun_ev) {
-      (void)hipEventSynchronize(rerun_ev);
-      (void)hipEventDestroy(rerun_ev);
-    }
-    h_rerun.release();
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
+};
+
+// =====================================================================================
+// Crate API mirror: ReedSolomonEncoder / ReedSolomonDecoder (one codeword, host memory)
+// =====================================================================================
+// An object made by *_new_on_device owns its context (`owned`: created with it, destroyed by
+// its _free), so objects made that way share no state and may run on different threads at
+// once; *_new borrows the caller's context, shared with whatever else uses it.
+// Each encoder / decoder stages its codeword in its own mapped pinned buffer (the shards are
+// copied there by add_*_shard, the device reads and writes it in place, and the result
+// accessors point into it), so no call re-copies or re-zeroes a 64 KiB slice.
+// `owned` is declared first, so it is destroyed last: the staging is freed before its context.
+namespace ag {
+namespace host __attribute__((visibility("hidden"))) {
+struct CtxDestroy {
+  void operator()(ag_rs_ctx* c) const { ag_rs_ctx_destroy(c); }
+};
+using OwnedCtx = std::unique_ptr<ag_rs_ctx, CtxDestroy>;
+}  // namespace host
+}  // namespace ag
+
+struct ag_rs_encoder {
+  ag::host::OwnedCtx owned;
+  ag_rs_ctx* ctx = nullptr;
+  size_t k = 0, m = 0, S = 0;
+  size_t received = 0;
+  bool encoded = false;
+  PinBuf pin;  // originals [k * S] then recovery shards [m * S]
+  uint8_t* orig() const { return pin.as<uint8_t>(); }
+  uint8_t* rec() const { return pin.as<uint8_t>() + k * S; }
+};
+
+struct ag_rs_decoder {
+  ag::host::OwnedCtx owned;
+  ag_rs_ctx* ctx = nullptr;
+  size_t k = 0, m = 0, S = 0;
+  std::vector<uint8_t> opres, rpres;
+  size_t no = 0, nr = 0;
+  bool decoded = false;
+  std::vector<uint8_t> restored;  // 1 where original i was restored by the last decode
+  PinBuf pin;  // originals [k * S], recovery shards [m * S], re-encoded coding shards [m * S]
+  uint8_t* orig() const { return pin.as<uint8_t>(); }
+  uint8_t* rec() const { return pin.as<uint8_t>() + k * S; }
 };
 
 // What the host translation units call in each other; each is documented where it is defined.
@@ -371,9 +432,28 @@ int decode_device(ag_rs_ctx* c, size_t k, size_t m, size_t S, size_t nblocks, ui
                   int mode);
 
 constexpr size_t kDataShreds = AG_RS_DATA_SHREDS;
-constexpr size_t kMaxPayload = kDataShreds * AG_RS_MAX_DATA_PER_SHRED - 1;
+constexpr size_t kTotalShreds = AG_RS_TOTAL_SHREDS;
+constexpr size_t kMaxAfterPadding = kDataShreds * AG_RS_MAX_DATA_PER_SHRED;
+constexpr size_t kMaxPayload = kMaxAfterPadding - 1;
+constexpr size_t kMaxSigBatch = size_t{1} << 31;  // shreds / slices per signature, validation or wire call
 
-// rs_api.cpp: what the composed shredders (shredder_api.cpp) call
+// rs_api.cpp: what the coder handle (rs_coder_api.cpp) calls
+int run_one_decode(ag_rs_ctx* c, size_t k, size_t m, size_t S, PinBuf& pin, const uint8_t* opres,
+                   const uint8_t* rpres, int mode, bool coding, const uint8_t** coding_src);
+
+// rs_coder_api.cpp: what the composed shredders (shredder_api.cpp) and the per-call server call
+ag::XformParams codeword_xform(uint8_t* cw, size_t cw_stride, size_t S, size_t n, size_t cps);
+ag::DecodeXParams codeword_decode_x(uint8_t* cw, size_t cw_stride, size_t S, size_t n, size_t cps);
+int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                       int64_t* plen, size_t m, bool no_surplus = false);
+int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
+                           const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
+                           bool reencode, int64_t* plen, bool exact = false);
+int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t** d_sizes, const uint32_t** d_col_base,
+                     uint32_t* total_columns);
+bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);
+
+// crypto_api.cpp: what the composed shredders call
 int ensure_empty_roots(ag_rs_ctx* c);
 int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
                       size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
@@ -389,14 +469,6 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
                         size_t leaf_nodes_stride = 0, uint32_t leaves_per_tree = 0, size_t group_stride = 0,
                         uint32_t skip_row = 0, bool roots_ready = false, const uint32_t* leaf_sizes = nullptr,
                         uint32_t size_group = 0);
-int pipe_coder_deshred(ag_rs_ctx* c, size_t n, size_t S, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
-                       int64_t* plen, size_t m, bool no_surplus = false);
-int pipe_coder_deshred_var(ag_rs_ctx* c, size_t n, uint8_t* cw, size_t cw_stride, const uint64_t* d_present,
-                           const uint32_t* d_sizes, const uint32_t* d_col_base, uint32_t total_columns,
-                           bool reencode, int64_t* plen, bool exact = false);
-int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t** d_sizes, const uint32_t** d_col_base,
-                     uint32_t* total_columns);
-bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);
 
 }  // namespace host
 }  // namespace ag

@@ -1,5 +1,5 @@
-// The batch encode / decode over device memory behind the C ABI (rs_api.cpp calls
-// encode_device / decode_device): which kernel serves a geometry and a shard size, the
+// The batch encode / decode over device memory behind the C ABI (rs_api.cpp and rs_coder_api.cpp
+// call encode_device / decode_device): which kernel serves a geometry and a shard size, the
 // restride of sizes that are not whole 64-byte chunks, and one launcher per decoder class
 // (rs_patterns.cpp's classify_patterns decides the class of every erasure pattern; this file
 // uploads what the class's kernel reads and launches it).
@@ -333,10 +333,8 @@ int decode_cols_device_patterns(const DecodeCall& d) {
   ag_rs_ctx* c = d.c;
   const size_t n = d.nblocks;
   int st;
-  if (c->present_ev) AG_HIP(hipEventSynchronize(c->present_ev));  // the previous upload has read h_present
-  else AG_HIP(hipEventCreateWithFlags(&c->present_ev, hipEventDisableTiming));
-  if ((st = c->h_present.ensure(n * 8))) return st;
-  uint64_t* pres = c->h_present.as<uint64_t>();
+  uint64_t* pres;
+  if ((st = c->present.host(n * 8, &pres))) return st;
   bool full_data = false;
   (void)pack_present_words(d.opres, d.rpres, m, n, pres, &full_data);
   size_t restore = 0;
@@ -350,17 +348,16 @@ int decode_cols_device_patterns(const DecodeCall& d) {
   c->last_classes[kNone] += n - restore;
   c->last_classes[kWindow64] += restore;
   if (!restore) return AG_RS_OK;
-  if ((st = c->ensure_tables()) || (st = c->d_present.ensure(n * 8, c->stream)) ||
+  if ((st = c->ensure_tables()) || (st = c->present.dev.ensure(n * 8, c->stream)) ||
       (st = c->d_pipe_few.ensure(n, c->stream)) || (st = c->xmask.dev.ensure(3 * n * 8, c->stream)) ||
       (st = c->d_rows.ensure(n * W * 4, c->stream)))
     return st;
   c->xmask.key.clear();  // xmask.dev / d_rows no longer hold run_window64's cached patterns
   c->xmask_w = 0;
-  AG_HIP(hipMemcpyAsync(c->d_present.ptr, pres, n * 8, hipMemcpyHostToDevice, c->stream));
-  AG_HIP(hipEventRecord(c->present_ev, c->stream));
+  if ((st = c->present.send(n * 8, c->stream))) return st;  // (the device buffer grown above: the old order)
   uint64_t* xm = c->xmask.dev.as<uint64_t>();
   uint32_t* rows = c->d_rows.as<uint32_t>();
-  if (launch_pipe_patterns(c->d_present.as<uint64_t>(), n, xm, c->d_pipe_few.as<uint8_t>(), false, c->stream) !=
+  if (launch_pipe_patterns(c->present.dev.as<uint64_t>(), n, xm, c->d_pipe_few.as<uint8_t>(), false, c->stream) !=
           hipSuccess ||
       launch_decode_rows(xm, xm + n, static_cast<uint32_t>(n), static_cast<uint32_t>(W), c->dtables(), rows, true,
                          c->stream) != hipSuccess)

@@ -1,9 +1,9 @@
 // Host side of the composed shredders: ag_shredder_shred_batch[_var|_kind] and
 // ag_shredder_deshred_batch[_var|_kind] (include/alpenglow_rs.h), the four shredders of shredder.rs
-// (Regular, CodingOnly, PETS, AONT) chained on the device from the batched stages of rs_api.cpp
-// (slice framing, ReedSolomonCoder, Merkle trees, signatures, all-or-nothing transforms; the
-// coder's encode / decode dispatch is rs_dispatch.cpp) and
-// the glue kernels of shredder.hip / wire.hip.
+// (Regular, CodingOnly, PETS, AONT) chained on the device from the batched stages of
+// rs_coder_api.cpp, crypto_api.cpp and wire_api.cpp (slice framing, ReedSolomonCoder, Merkle trees,
+// signatures, all-or-nothing transforms; the coder's encode / decode dispatch is rs_dispatch.cpp)
+// and the glue kernels of shredder.hip / wire.hip.
 //
 // The entry points keep what is their own (argument checks, framing, the coder call, how a
 // failed slice is decoded again) and share the stages around it: the row layout as data
@@ -523,11 +523,9 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
   const bool regular = k.aon < 0 && k.m == kDataShreds;
   int st;
   // list | sizes | column prefix through pinned staging, rewritten once its last upload completed
-  if (c->rerun_ev) AG_HIP(hipEventSynchronize(c->rerun_ev));
-  else AG_HIP(hipEventCreateWithFlags(&c->rerun_ev, hipEventDisableTiming));
   const size_t words = 3 * R + 1;
-  if ((st = c->h_rerun.ensure(4 * words))) return st;
-  uint32_t* h = c->h_rerun.as<uint32_t>();
+  uint32_t* h;
+  if ((st = c->rerun.host(4 * words, &h))) return st;
   size_t max_s = 0;
   uint32_t cols = 0;
   for (size_t r = 0; r < R; ++r) {
@@ -545,8 +543,7 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
       (st = pipe_buf(c, kBufRerunMeta, (32 + 32 + 8 + 1) * R, &meta)) ||
       (st = pipe_buf(c, kBufRerunProofs, R * ag::kPipeShreds * kPipeProofBytes, &c_proofs)))
     return st;
-  AG_HIP(hipMemcpyAsync(d_list, h, 4 * words, hipMemcpyHostToDevice, c->stream));
-  AG_HIP(hipEventRecord(c->rerun_ev, c->stream));
+  if ((st = c->rerun.send(4 * words, c->stream, d_list))) return st;
   const uint32_t* d_sizes = reinterpret_cast<const uint32_t*>(d_list) + R;
   ag::PipeRerunParams rp{};
   rp.list = reinterpret_cast<const uint32_t*>(d_list);
@@ -799,7 +796,7 @@ int ag_shredder_shred_batch(ag_rs_ctx* c, size_t nslices, size_t S, const uint8_
 
 // RegularShredder::shred over slices of mixed shred sizes: the stages of ag_shredder_shred_batch,
 // each taking one size per slice -- the var coder (one launch set for the whole mix), the var
-// Merkle build over the size table the coder uploaded (d_lens: lens | sizes | column prefix; it
+// Merkle build over the size table the coder uploaded (lens.dev: lens | sizes | column prefix; it
 // stays valid on the stream until the next coder call), the serializer with a row size per slice.
 int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* parent_flags, const uint8_t* parent_ids,
                                 const uint8_t* data, size_t data_stride, const uint32_t* data_lens,
@@ -853,7 +850,7 @@ int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* par
                                         shred_bytes_out)))
     return st;
   if (!(c->last_encode_kernels & ag::kEkVar)) return AG_RS_ERR_DEVICE;  // (16-byte-aligned codewords: always var)
-  const uint32_t* d_sizes = c->d_lens.as<uint32_t>() + n;
+  const uint32_t* d_sizes = c->lens.dev.as<uint32_t>() + n;
   // 3. slice Merkle trees, 4. slice signatures, 5. the 64 datagrams per slice (rows and data
   //    lengths at the slice's own size), 6. the block hashes over the roots
   return shred_tail(c, k, n, 0, d_sizes, codewords, codeword_stride, slots, slice_indices, is_last, seed, pk,

@@ -1,0 +1,235 @@
+"""The staging-reuse rule of the calls that upload host arguments behind the queued work (lengths,
+sizes, block offsets, present words: StagedUpload in csrc/rs_ctx.hpp): the pinned staging is
+rewritten -- and here regrown -- only after the previous call's upload of it has completed.
+
+Each entry point that returns before its work completes is called with 2 slices and again at once,
+on the same context and with nothing synchronised in between, with other contents and 70 slices;
+both results are then compared with the oracles the neighbouring tests use (rs_oracle's
+ReedSolomonCoder, merkle_oracle's trees).  The two synchronous deshreds run once each, with
+per-slice patterns, directly behind a shred.
+"""
+
+import random
+
+import numpy as np
+import pytest
+
+import merkle_oracle as mk
+import rs_oracle as o
+from alpenglow_amd import rs
+
+N1, N2 = 2, 70           # the second batch is larger: its staging has to grow
+M = 32                   # coding shreds
+S_UNI = 64               # the uniform calls' shred size
+VAR_SIZES = (2, 64, 66)  # one column, one whole chunk, a chunk and a 2-byte tail
+VAR_STRIDE = 64 * 66 + 64
+NODES = 32 * 127         # a 64-leaf tree's nodes
+PROOFS = 64 * 6 * 32     # and its 64 proofs
+FILL = 0xA5              # bytes the calls must not write
+ABSENT = 0x5A            # shreds that did not arrive
+
+torch = None
+
+
+@pytest.fixture(scope="module")
+def dev(ctx):
+    """All torch work and every library launch go to one explicit (non-null) stream."""
+    global torch
+    import torch as _torch
+
+    torch = _torch
+    d = torch.device("cuda:0")
+    s = torch.cuda.Stream(d)
+    torch.cuda.set_stream(s)
+    ctx.set_stream(s.cuda_stream)
+    return d
+
+
+def to_dev(a, dev):
+    return torch.from_numpy(np.array(a, copy=True)).to(dev)
+
+
+class Slices:
+    """Seeded payloads of the given shred sizes, the oracle's codewords, and per slice exactly 32
+    kept shreds with the oracle's deshred of them (computed once, shared, read-only)."""
+
+    def __init__(self, sizes, seed):
+        rng = random.Random(seed)
+        self.sizes = list(sizes)
+        self.n = len(self.sizes)
+        self.lens = [rng.randrange(32 * S - 64, 32 * S) for S in self.sizes]  # reed_solomon.rs:94-95
+        self.payloads = [o.splitmix64_bytes(seed * 1000 + b, L) for b, L in enumerate(self.lens)]
+        self.codewords, self.keep, self.deshred = [], [], []
+        for p, S in zip(self.payloads, self.sizes):
+            raw = o.coder_shred(p, M)
+            c = b"".join(raw.data) + b"".join(raw.coding)
+            keep = set(rng.sample(range(64), 32))
+            orig = {i: c[i * S:(i + 1) * S] for i in range(32) if i in keep}
+            rec = {j: c[(32 + j) * S:(33 + j) * S] for j in range(M) if 32 + j in keep}
+            payload, out = o.coder_deshred_indexed(orig, rec, M)
+            self.codewords.append(c)
+            self.keep.append(keep)
+            self.deshred.append((len(payload), b"".join(out.data) + b"".join(out.coding)))
+
+    def part(self, a, b):
+        import copy
+
+        other = copy.copy(self)
+        for name in ("sizes", "lens", "payloads", "codewords", "keep", "deshred"):
+            setattr(other, name, getattr(self, name)[a:b])
+        other.n = b - a
+        return other
+
+    def device_payloads(self, dev):
+        pay = np.zeros((self.n, 32 * max(self.sizes)), np.uint8)
+        for b, p in enumerate(self.payloads):
+            pay[b, :len(p)] = np.frombuffer(p, np.uint8)
+        return to_dev(pay, dev)
+
+    def device_codewords(self, dev, stride, damaged=False):
+        cw = np.full((self.n, stride), FILL, np.uint8)
+        for b, (c, S) in enumerate(zip(self.codewords, self.sizes)):
+            cw[b, :len(c)] = np.frombuffer(c, np.uint8)
+            for i in range(64 if damaged else 0):
+                if i not in self.keep[b]:
+                    cw[b, i * S:(i + 1) * S] = ABSENT
+        return to_dev(cw, dev)
+
+    def flags(self):
+        dp = np.array([[1 if i in k else 0 for i in range(32)] for k in self.keep], np.uint8)
+        cp = np.array([[1 if 32 + j in k else 0 for j in range(M)] for k in self.keep], np.uint8)
+        return dp, cp
+
+    def check_codewords(self, d_cw, want=None):
+        host = d_cw.cpu().numpy()
+        for b, S in enumerate(self.sizes):
+            c = self.codewords[b] if want is None else want[b]
+            assert host[b, :64 * S].tobytes() == c, (self.n, b, S)
+            assert (host[b, 64 * S:] == FILL).all(), (self.n, b, S)
+
+
+@pytest.fixture(scope="module")
+def uniform():
+    return Slices([S_UNI] * (N1 + N2), 31)
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    sizes = [VAR_SIZES[b % 3] for b in range(N1 + N2)]
+    random.Random(9).shuffle(sizes)
+    sizes[:N1] = [2, 66]  # the first call's staging holds the smallest table there is
+    return Slices(sizes, 32)
+
+
+def two_batches(batch):
+    return batch.part(0, N1), batch.part(N1, N1 + N2)
+
+
+@pytest.mark.gpu
+def test_coder_shred_batch_twice(ctx, dev, uniform):
+    parts = two_batches(uniform)
+    stride = 64 * S_UNI
+    pays = [p.device_payloads(dev) for p in parts]
+    cws = [torch.full((p.n, stride), FILL, dtype=torch.uint8, device=dev) for p in parts]
+    ctx.synchronize()
+    for p, pay, cw in zip(parts, pays, cws):  # back to back: nothing waits for the first call's upload
+        rs.coder_shred_batch(ctx, M, p.n, S_UNI, pay, pay.shape[1], p.lens, cw, stride)
+    ctx.synchronize()
+    for p, cw in zip(parts, cws):
+        p.check_codewords(cw)
+
+
+@pytest.mark.gpu
+def test_coder_shred_batch_var_twice(ctx, dev, mixed):
+    parts = two_batches(mixed)
+    pays = [p.device_payloads(dev) for p in parts]
+    cws = [torch.full((p.n, VAR_STRIDE), FILL, dtype=torch.uint8, device=dev) for p in parts]
+    ctx.synchronize()
+    sizes = []
+    for p, pay, cw in zip(parts, pays, cws):
+        sizes.append(rs.coder_shred_batch_var(ctx, M, p.n, pay, pay.shape[1], p.lens, cw, VAR_STRIDE))
+        assert rs.last_encode_kernels(ctx) == {"var_encode"}
+    ctx.synchronize()
+    for p, got, cw in zip(parts, sizes, cws):
+        assert list(got) == p.sizes
+        p.check_codewords(cw)
+
+
+@pytest.mark.gpu
+def test_merkle_build_batch_var_twice(ctx, dev, mixed):
+    parts = two_batches(mixed)
+    leaves = [p.device_codewords(dev, VAR_STRIDE) for p in parts]
+    outs = [[torch.full((p.n, w), FILL, dtype=torch.uint8, device=dev) for w in (32, NODES, PROOFS)] for p in parts]
+    ctx.synchronize()
+    for p, lv, (roots, nodes, proofs) in zip(parts, leaves, outs):
+        rs.merkle_build_batch_var(ctx, p.n, p.sizes, lv, VAR_STRIDE, roots, nodes, NODES, proofs, PROOFS)
+    ctx.synchronize()
+    for p, out in zip(parts, outs):
+        roots, nodes, proofs = (t.cpu().numpy() for t in out)
+        for b, (c, S) in enumerate(zip(p.codewords, p.sizes)):
+            rows = [c[j * S:(j + 1) * S] for j in range(64)]
+            t = mk.slice_tree(rows[:32], rows[32:])
+            assert roots[b].tobytes() == t.root(), (p.n, b, S)
+            assert nodes[b].tobytes() == b"".join(t.nodes), (p.n, b, S)
+            assert proofs[b].tobytes() == b"".join(b"".join(t.create_proof(j)) for j in range(64)), (p.n, b, S)
+
+
+@pytest.mark.gpu
+def test_block_tree_batch_twice(ctx, dev):
+    rng = random.Random(5)
+    counts = [[1, 3], [rng.choice((1, 3)) for _ in range(N2)]]
+    roots = [np.frombuffer(o.splitmix64_bytes(0xB10C + i, 32 * sum(c)), np.uint8).reshape(-1, 32)
+             for i, c in enumerate(counts)]
+    pstride = 32 * 2 * 3  # a 3-leaf tree: height 2
+    d_roots = [to_dev(r.reshape(-1), dev) for r in roots]
+    hashes = [torch.full((len(c), 32), FILL, dtype=torch.uint8, device=dev) for c in counts]
+    proofs = [torch.zeros((len(c), pstride), dtype=torch.uint8, device=dev) for c in counts]
+    ctx.synchronize()
+    for c, r, h, p in zip(counts, d_roots, hashes, proofs):
+        rs.block_tree_batch(ctx, len(c), c, r, h, None, 0, p, pstride)
+    ctx.synchronize()
+    for c, r, h, p in zip(counts, roots, hashes, proofs):
+        h, p, at = h.cpu().numpy(), p.cpu().numpy(), 0
+        for b, n in enumerate(c):
+            t = mk.MerkleTree([r[at + j].tobytes() for j in range(n)])
+            want = b"".join(b"".join(t.create_proof(j)) for j in range(n))
+            assert h[b].tobytes() == t.root(), (len(c), b, n)
+            assert p[b, :len(want)].tobytes() == want and not p[b, len(want):].any(), (len(c), b, n)
+            at += n
+
+
+@pytest.mark.gpu
+def test_coder_deshred_batch_behind_a_shred(ctx, dev, uniform):
+    small, big = two_batches(uniform)
+    stride = 64 * S_UNI
+    pay = small.device_payloads(dev)
+    cw = torch.full((small.n, stride), FILL, dtype=torch.uint8, device=dev)
+    damaged = big.device_codewords(dev, stride, damaged=True)
+    dp, cp = big.flags()
+    ctx.synchronize()
+    rs.coder_shred_batch(ctx, M, small.n, S_UNI, pay, pay.shape[1], small.lens, cw, stride)
+    res = rs.coder_deshred_batch(ctx, M, big.n, S_UNI, damaged, stride, dp, cp, rs.DECODE_EXACT, as_array=True)
+    assert rs.last_window_kernels(ctx), "per-slice patterns of exactly 32 shreds decode on the device-pattern path"
+    ctx.synchronize()
+    small.check_codewords(cw)
+    assert list(res) == [d[0] for d in big.deshred] == big.lens
+    big.check_codewords(damaged, [d[1] for d in big.deshred])
+
+
+@pytest.mark.gpu
+def test_coder_deshred_batch_var_behind_a_shred(ctx, dev, mixed):
+    small, big = two_batches(mixed)
+    pay = small.device_payloads(dev)
+    cw = torch.full((small.n, VAR_STRIDE), FILL, dtype=torch.uint8, device=dev)
+    damaged = big.device_codewords(dev, VAR_STRIDE, damaged=True)
+    dp, cp = big.flags()
+    ctx.synchronize()
+    sizes = rs.coder_shred_batch_var(ctx, M, small.n, pay, pay.shape[1], small.lens, cw, VAR_STRIDE)
+    res = rs.coder_deshred_batch_var(ctx, M, big.n, big.sizes, damaged, VAR_STRIDE, dp, cp, rs.DECODE_ANY_K,
+                                     as_array=True)
+    assert "var_decode" in rs.last_window_kernels(ctx)
+    ctx.synchronize()
+    assert list(sizes) == small.sizes
+    small.check_codewords(cw)
+    assert list(res) == [d[0] for d in big.deshred] == big.lens
+    big.check_codewords(damaged, [d[1] for d in big.deshred])
