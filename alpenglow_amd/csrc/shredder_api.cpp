@@ -432,15 +432,20 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
 // Shredder::deshred's result per slice from the coder's (plen: payload length or -error), the
 // Merkle check's (h_same) and SlicePayload::try_from's (sstat): status, ok, and the slice's
 // header for the slices that succeeded (zero for the others).
+// key_bytes (PETS / AONT: the key tail, else 0): decrypt_payload runs inside
+// deshred_validated_shreds, before check_merkle_tree (shredder.rs:293, :303), so a decoded buffer
+// shorter than the key is BadEncoding whatever the root comparison says.  A slice whose tree
+// differs was never decrypted (pass 0's and the EXACT re-run's alike), so its plen is still the
+// coder's buffer length: this is the one place both kinds of entries go through.
 void pipe_statuses(size_t n, const int64_t* plen, const uint8_t* h_same, const uint8_t* sstat, const PipeMeta& h,
-                   int32_t* status, uint8_t* ok, uint64_t* slots_out, uint64_t* slice_indices_out,
+                   size_t key_bytes, int32_t* status, uint8_t* ok, uint64_t* slots_out, uint64_t* slice_indices_out,
                    uint8_t* is_last_out) {
   for (size_t s = 0; s < n; ++s) {
     int32_t r = AG_RS_OK;
     if (plen[s] < 0) {
       r = -plen[s] == AG_RS_ERR_INVALID_PADDING ? AG_RS_ERR_BAD_ENCODING : static_cast<int32_t>(-plen[s]);
     } else if (!h_same[s]) {
-      r = AG_RS_ERR_INVALID_MERKLE_TREE;
+      r = plen[s] < static_cast<int64_t>(key_bytes) ? AG_RS_ERR_BAD_ENCODING : AG_RS_ERR_INVALID_MERKLE_TREE;
     } else if (sstat[s] == AG_SLICE_TOO_LARGE) {
       r = AG_RS_ERR_TOO_MUCH_DATA;
     } else if (sstat[s] != AG_SLICE_OK) {
@@ -752,7 +757,7 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
     }
   }
   std::vector<uint8_t> ok(n);
-  pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
+  pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, 0, status, ok.data(), slots_out, slice_indices_out,
                 is_last_out);
   // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
   uint8_t* d_ok;
@@ -983,6 +988,9 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   // lengths change only in step 7 (PETS / AONT serialize the absent datagrams before decrypting,
   // into length-0 slots that a redo parses as absent), so a redo starts from the same datagrams.
   c->last_rerun_slices = c->last_rerun_passes = 0;
+  // (test aids: the device-pattern pass only adds to them, the coder's host-pattern route resets them)
+  c->last_encode_kernels = c->last_window_kernels = 0;
+  const size_t key_bytes = k.aon >= 0 ? ag::kCipherKeyBytes : 0;
   DeshredViews v;
   std::vector<uint8_t> ok(n), pre_ok(n), h_same(n), sstat(n);
   std::vector<int64_t> plen(n);
@@ -1086,7 +1094,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     }
     if (k.aon >= 0) {
       // the absent datagrams of the slices that decoded and match their root, serialized from
-      // the encrypted rows; then decrypt_payload (BadEncoding for a failed key check)
+      // the encrypted rows; then decrypt_payload (BadEncoding for a buffer shorter than the key)
       for (size_t s = 0; s < n; ++s) pre_ok[s] = plen[s] >= 0 && h_same[s];
       if ((st = fill_missing(c, k, n, S, v, pre_ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
       AG_HIP(hipStreamSynchronize(c->stream));
@@ -1099,7 +1107,8 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
         for (size_t s = 0; s < n; ++s) {
           pl[s] = cl[s] < ag::kCipherKeyBytes ? -AG_RS_ERR_BAD_ENCODING
                                               : static_cast<int64_t>(cl[s]) - ag::kCipherKeyBytes;
-          if (cl[s] < ag::kCipherKeyBytes) cl[s] = ag::kCipherKeyBytes;  // no-op
+          // a failed slice (cl 0) or a buffer shorter than the key: a keystream of zero bytes
+          if (cl[s] < ag::kCipherKeyBytes) cl[s] = ag::kCipherKeyBytes;
         }
         ag::BufferBatch bb;
         if ((st = aon_batch(c, n, codewords, cw_stride, cl.data(), 0, &bb)) ||
@@ -1121,8 +1130,8 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
                                    parent_ids_out, data_offsets_out, data_lens_out)))
       return st;
-    pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out, slice_indices_out,
-                  is_last_out);
+    pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, key_bytes, status, ok.data(), slots_out,
+                  slice_indices_out, is_last_out);
     return AG_RS_OK;
   };
   // the side-stream rule for AONT's SHA-256, which a pass forks in step 4 and joins in step
@@ -1153,7 +1162,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
         data_offsets_out[s] = rr.data_offset[r];
         data_lens_out[s] = rr.data_len[r];
       }
-      pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, status, ok.data(), slots_out,
+      pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, key_bytes, status, ok.data(), slots_out,
                     slice_indices_out, is_last_out);
     }
   }

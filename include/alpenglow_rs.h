@@ -619,7 +619,7 @@ int ag_shredder_deshred_batch_var(ag_rs_ctx* ctx, size_t nslices, const uint32_t
  * shred (EXACT: a batch decodes ANY_K on the device, and the slices that then fail the padding
  * or the Merkle check with surplus shreds -- only those -- are decoded again with EXACT in one
  * batched pass), decrypts after the raw shreds are taken (decrypt_payload: BadEncoding
- * for a buffer shorter than the key or a failed key check, :512-528), then check_merkle_tree,
+ * for a buffer shorter than the key, :512-528, whatever the tree then says), then check_merkle_tree,
  * SlicePayload::try_from and fill_missing_shreds as ag_shredder_deshred_batch; the parsed data
  * is at codewords + s * codeword_stride + data_offsets_out[s].  The datagrams are parsed into
  * and serialized from their codeword rows.  PETS / AONT serialize the absent datagrams before
