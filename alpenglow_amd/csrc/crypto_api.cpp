@@ -43,15 +43,15 @@ int merkle_var_check(size_t nslices, const uint32_t* leaf_bytes, const uint8_t* 
   return AG_RS_OK;
 }
 
+}  // namespace
+
+namespace ag::host {
 int ensure_ed_base(ag_rs_ctx* c) {
   if (c->d_ed_base.ptr) return AG_RS_OK;
   int st = c->d_ed_base.ensure(ag::kEdBaseTableBytes, c->stream);
   if (st) return st;
   return ag::launch_ed25519_init(c->d_ed_base.as<int32_t>(), c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
-}  // namespace
-
-namespace ag::host {
 int ensure_empty_roots(ag_rs_ctx* c) {
   if (c->d_empty_roots.ptr) return AG_RS_OK;
   uint32_t er[ag::kMerkleMaxHeight][8];

@@ -1,0 +1,218 @@
+// Host side of ag_shredder_intake_batch (include/alpenglow_rs.h section 10): the argument
+// checks, the window upload, the carve-up of the context's intake scratch and the fixed chain of
+// launches -- the wire parse (wire.hip), the intake kernels (intake.hip), the Merkle root
+// derivation (merkle.hip) and at most two Ed25519 verify launches (ed25519.hip).  Every launch
+// is made whatever the datagrams hold; ordering is the stream's.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <numeric>
+#include <vector>
+
+#include "../../include/alpenglow_rs.h"
+#include "ed25519.hpp"
+#include "intake.hpp"
+#include "merkle.hpp"
+#include "rs_ctx.hpp"
+#include "shredder.hpp"
+#include "wire.hpp"
+
+using namespace ag::host;
+
+namespace {
+
+constexpr size_t kIntakeMax = size_t{1} << 24;  // datagrams per call, rows per window
+constexpr size_t kProofBytes = 32 * ag::kPipeHeight;
+
+// Sections of the scratch buffer, each 256-byte aligned.
+struct Carver {
+  uint8_t* base;
+  size_t used = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* out = base ? reinterpret_cast<T*>(base + used) : nullptr;
+    used += (count * sizeof(T) + 255) / 256 * 256;
+    return out;
+  }
+};
+
+struct IntakeScratch {
+  ag::ShredColumns cols{};
+  uint8_t *wire, *plausible, *roots, *commit, *ok;
+  uint32_t *row, *meta, *mlist, *list1, *list2, *counts, *pick, *out;
+  size_t zero_bytes, none_bytes;  // [ok, counts] is one zeroed span, [pick .. claim] one of kIntakeNone
+  uint32_t *setter, *tstar, *claim;
+};
+
+// Lays the sections out from `base` (null: only the size is wanted); returns the bytes used.
+size_t carve(uint8_t* base, size_t n, size_t nrows, size_t nslots, IntakeScratch* s) {
+  Carver c{base};
+  s->cols.kind = c.take<uint8_t>(n);
+  s->cols.slot = c.take<uint64_t>(n);
+  s->cols.slice_index = c.take<uint64_t>(n);
+  s->cols.is_last = c.take<uint8_t>(n);
+  s->cols.shred_index = c.take<uint32_t>(n);
+  s->cols.data = c.take<uint8_t>(n * ag::kPipeMaxShredBytes);
+  s->cols.data_stride = ag::kPipeMaxShredBytes;
+  s->cols.data_len = c.take<uint32_t>(n);
+  s->cols.sig = c.take<uint8_t>(n * 64);
+  s->cols.proof = c.take<uint8_t>(n * kProofBytes);
+  s->cols.proof_stride = kProofBytes;
+  s->cols.height = c.take<uint32_t>(n);
+  s->wire = c.take<uint8_t>(n);
+  s->plausible = c.take<uint8_t>(n);
+  s->roots = c.take<uint8_t>(n * 32);
+  s->commit = c.take<uint8_t>(n * ag::kIntakeCommitStride);
+  s->row = c.take<uint32_t>(n);
+  s->meta = c.take<uint32_t>(n);
+  s->mlist = c.take<uint32_t>(n + 1);
+  s->list1 = c.take<uint32_t>(std::min(n, nrows));
+  s->list2 = c.take<uint32_t>(n);
+  s->out = c.take<uint32_t>(2 * nrows);
+  size_t at = c.used;
+  s->ok = c.take<uint8_t>(n);
+  s->counts = c.take<uint32_t>(2);
+  s->zero_bytes = c.used - at;
+  at = c.used;
+  s->pick = c.take<uint32_t>(nrows);
+  s->setter = c.take<uint32_t>(nrows);
+  s->tstar = c.take<uint32_t>(nslots);
+  s->claim = c.take<uint32_t>(ag::kPipeShreds * nrows);
+  s->none_bytes = c.used - at;
+  return c.used;
+}
+
+}  // namespace
+
+int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_ids, size_t slices_per_slot, size_t n,
+                             const uint8_t* rx, size_t rx_stride, const uint32_t* rx_lens, const uint8_t* pk,
+                             uint8_t* packets, size_t packet_stride, uint32_t* packet_lens, uint8_t* commitments,
+                             uint32_t* shred_bytes, int32_t* last_slice, uint8_t* verdict, uint32_t* shred_bytes_out,
+                             uint32_t* counts_out) {
+  size_t need = 0;
+  if (!c || nslots == 0 || nslots >= kIntakeMax || slices_per_slot == 0 ||
+      slices_per_slot > ag::kMaxSlicesPerBlock || nslots * slices_per_slot >= kIntakeMax || n >= kIntakeMax ||
+      !slot_ids || !packets || !packet_lens || !commitments || !shred_bytes || !last_slice ||
+      (n && (!rx || !rx_lens || !pk || !verdict)) ||
+      ag_shred_datagram_bytes(AG_RS_MAX_DATA_PER_SHRED, ag::kPipeHeight, &need) || packet_stride < need ||
+      packet_stride % 16 || reinterpret_cast<uintptr_t>(packets) % 16 ||
+      (n && (rx_stride < need || rx_stride % 16 || reinterpret_cast<uintptr_t>(rx) % 16)))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  const size_t nrows = nslots * slices_per_slot;
+  // the window sorted by slot id (the kernels search it), each id with the caller's index
+  std::vector<uint32_t> order(nslots);
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return slot_ids[a] < slot_ids[b]; });
+  for (size_t i = 1; i < nslots; ++i)
+    if (slot_ids[order[i]] == slot_ids[order[i - 1]]) return AG_RS_ERR_INVALID_ARGUMENT;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+
+  int st;
+  uint8_t* win = nullptr;
+  if ((st = c->intake_win.host(12 * nslots, &win))) return st;
+  for (size_t i = 0; i < nslots; ++i) {
+    reinterpret_cast<uint64_t*>(win)[i] = slot_ids[order[i]];
+    reinterpret_cast<uint32_t*>(win + 8 * nslots)[i] = order[i];
+  }
+  if ((st = c->intake_win.send(12 * nslots, c->stream))) return st;
+  IntakeScratch s;
+  if ((st = c->d_intake.ensure(carve(nullptr, n, nrows, nslots, &s), c->stream))) return st;
+  carve(c->d_intake.as<uint8_t>(), n, nrows, nslots, &s);
+  if ((st = c->h_intake.ensure(8 * nrows))) return st;
+  hipStream_t q = c->stream;
+
+  ag::IntakeParams p{};
+  p.n = n;
+  p.nslots = static_cast<uint32_t>(nslots);
+  p.spp = static_cast<uint32_t>(slices_per_slot);
+  p.nrows = static_cast<uint32_t>(nrows);
+  p.win_ids = c->intake_win.dev.as<uint64_t>();
+  p.win_w = reinterpret_cast<const uint32_t*>(c->intake_win.dev.as<uint8_t>() + 8 * nslots);
+  p.rx = rx;
+  p.rx_stride = rx_stride;
+  p.rx_lens = rx_lens;
+  p.packets = packets;
+  p.packet_stride = packet_stride;
+  p.packet_lens = packet_lens;
+  p.commitments = commitments;
+  p.shred_bytes = shred_bytes;
+  p.last_slice = last_slice;
+  p.verdict = verdict;
+  p.wire = s.wire;
+  p.slot = s.cols.slot;
+  p.slice_index = s.cols.slice_index;
+  p.height = s.cols.height;
+  p.row = s.row;
+  p.meta = s.meta;
+  p.plausible = s.plausible;
+  p.roots = s.roots;
+  p.commit = s.commit;
+  p.ok = s.ok;
+  p.list1 = s.list1;
+  p.list2 = s.list2;
+  p.counts = s.counts;
+  p.pick = s.pick;
+  p.setter = s.setter;
+  p.tstar = s.tstar;
+  p.claim = s.claim;
+  p.out = s.out;
+
+  AG_HIP(hipMemsetAsync(s.ok, 0, s.zero_bytes, q));
+  AG_HIP(hipMemsetAsync(s.pick, 0xFF, s.none_bytes, q));
+  if (n) {
+    if ((st = ensure_ed_base(c))) return st;
+    // parse + key: the datagrams' fields (payload, signature and path to aligned scratch rows),
+    // then verdicts 1-3, the window row and the rows' picks
+    AG_HIP(ag::launch_shred_deserialize(rx, rx_stride, rx_lens, n, s.cols, s.wire, q));
+    AG_HIP(ag::launch_intake_key(p, q));
+    // root and commitment of every plausible datagram (leaves of their own sizes)
+    ag::MerkleVerifyParams mv{};
+    mv.leaves = s.cols.data;
+    mv.leaf_stride = s.cols.data_stride;
+    mv.height = ag::kPipeHeight;
+    mv.index = s.cols.shred_index;
+    mv.proofs = s.cols.proof;
+    mv.proofs_stride = kProofBytes;
+    mv.n = n;
+    mv.roots_out = s.roots;
+    mv.active = s.plausible;
+    mv.list = s.mlist;
+    mv.leaf_sizes = s.cols.data_len;
+    mv.size_group = 1;
+    AG_HIP(ag::launch_merkle_verify(mv, q));
+    AG_HIP(ag::launch_intake_commit(p, q));
+    // cache resolution: the picks' signatures, then everything not equal to a valid cache
+    ag::EdVerifyParams ev{};
+    ev.pks = pk;
+    ev.pk_stride = 0;
+    ev.msgs = s.commit;
+    ev.msg_stride = ag::kIntakeCommitStride;
+    ev.msg_len = ag::kSliceCommitmentLen;
+    ev.sigs = s.cols.sig;
+    ev.sig_stride = 64;
+    ev.ok = s.ok;
+    ev.base_table = c->d_ed_base.as<int32_t>();
+    ev.n = std::min(n, nrows);
+    ev.list = s.list1;
+    ev.list_count = s.counts;
+    AG_HIP(ag::launch_ed25519_verify(ev, q));
+    AG_HIP(ag::launch_intake_classify(p, q));
+    ev.n = n;
+    ev.list = s.list2;
+    ev.list_count = s.counts + 1;
+    AG_HIP(ag::launch_ed25519_verify(ev, q));
+    AG_HIP(ag::launch_intake_setter(p, q));
+    AG_HIP(ag::launch_intake_accept(p, q));
+    // last slice per slot, the claim of the datagram slots, the copies
+    AG_HIP(ag::launch_intake_claim(p, q));
+    AG_HIP(ag::launch_intake_route(p, q));
+  }
+  AG_HIP(ag::launch_intake_finalize(p, q));
+  uint32_t* h = c->h_intake.as<uint32_t>();
+  AG_HIP(hipMemcpyAsync(h, s.out, 8 * nrows, hipMemcpyDeviceToHost, q));
+  AG_HIP(hipStreamSynchronize(q));
+  if (shred_bytes_out) std::memcpy(shred_bytes_out, h, 4 * nrows);
+  if (counts_out) std::memcpy(counts_out, h + nrows, 4 * nrows);
+  return AG_RS_OK;
+}

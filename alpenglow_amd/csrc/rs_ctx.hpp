@@ -1,6 +1,6 @@
 // The device context behind the C ABI (include/alpenglow_rs.h) and the helpers the host
 // translation units share: rs_api.cpp, rs_coder_api.cpp, crypto_api.cpp and wire_api.cpp (the C
-// ABI), rs_dispatch.cpp (the batch encode / decode dispatch) and shredder_api.cpp.  Internal: not
+// ABI), rs_dispatch.cpp (the batch encode / decode dispatch), shredder_api.cpp and intake_api.cpp.  Internal: not
 // installed, included only by the host .cpp files; nothing here is exported from the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -239,6 +239,9 @@ struct ag_rs_ctx {
   static constexpr int kPipeBufs = 37;
   DevBuf pipe[kPipeBufs];                   // composed shredder scratch (shredder_api.cpp's PipeBuf roles)
   DevBuf d_sh_roots, d_sh_commit, d_sh_onvalid, d_sh_list;  // shred validation scratch
+  DevBuf d_intake;                          // shred intake scratch (intake_api.cpp carves it up)
+  StagedUpload intake_win;                  // its window: slot ids ascending (u64), then their indices (u32)
+  PinBuf h_intake;                          // pinned staging of its per-row host outputs
   // host-memory calls: two staging slots, H2D / D2H streams next to the compute stream
   struct Slot {
     DevBuf in, out;
@@ -453,8 +456,9 @@ int upload_var_sizes(ag_rs_ctx* c, size_t n, const uint32_t* S, const uint32_t**
                      uint32_t* total_columns);
 bool pipe_tail_ok(size_t S, size_t m, bool no_reencode = false);
 
-// crypto_api.cpp: what the composed shredders call
+// crypto_api.cpp: what the composed shredders and the intake call
 int ensure_empty_roots(ag_rs_ctx* c);
+int ensure_ed_base(ag_rs_ctx* c);
 int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, const uint8_t* leaves,
                       size_t slice_stride, uint8_t* roots, uint8_t* nodes, size_t nodes_stride, uint8_t* proofs,
                       size_t proofs_stride);

@@ -86,6 +86,7 @@ EXPORTS = (
     "ag_slice_frame_batch", "ag_slice_parse_batch",
     "ag_shredder_shred_batch", "ag_shredder_deshred_batch", "ag_shredder_shred_batch_var",
     "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind", "ag_shredder_deshred_batch_var",
+    "ag_shredder_intake_batch",
 )
 
 
@@ -181,6 +182,7 @@ def load():
         "ag_shredder_shred_batch_kind": ([p, i, sz, sz, p, p, p, sz, p, p, p, p, p, p, p, p, sz, p, p, p, sz, p], i),
         "ag_shredder_deshred_batch_kind": ([p, i, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
         "ag_shredder_deshred_batch_var": ([p, sz, p, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
+        "ag_shredder_intake_batch": ([p, sz, p, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p], i),
     }
     sigs["ag_rs_internal_last_decode_classes"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_encode_kernels"] = ([p, p], i)  # test aid, not in the header
@@ -1196,3 +1198,35 @@ def shredder_deshred_batch_kind(ctx: Context, kind: int, nslices: int, shred_byt
            "ag_shredder_deshred_batch_kind")
     parents = _parent_list(flags, ids)
     return DeshredBatch(st, slots, sidx, last, parents, offs, dl)
+
+
+# ---- shred intake: received datagrams -> the slice slots of the deshreds ---------------------
+
+(INTAKE_STORED, INTAKE_MALFORMED, INTAKE_OUT_OF_WINDOW, INTAKE_IMPLAUSIBLE, INTAKE_INVALID_SIGNATURE,
+ INTAKE_EQUIVOCATION, INTAKE_SIZE_MISMATCH, INTAKE_DUPLICATE, INTAKE_PRUNED) = range(9)
+INTAKE_VERDICTS = ("stored", "malformed", "out_of_window", "implausible", "invalid_signature", "equivocation",
+                   "size_mismatch", "duplicate", "pruned")
+
+
+def shredder_intake_batch(ctx: Context, slot_ids, slices_per_slot: int, n: int, rx, rx_stride: int, rx_lens, pk,
+                          packets, packet_stride: int, packet_lens, commitments, shred_bytes, last_slice, verdict):
+    """ag_shredder_intake_batch: n datagrams in arrival order (device rx / rx_lens) are validated
+    as the reference's blockstore does (ValidatedShred::try_new with the row's cached commitment,
+    BlockData::add_shred's cache, last-slice and duplicate rules) and copied into the caller's
+    store (device: packets / packet_lens as the deshreds take them, commitments 49 B per row,
+    shred_bytes u32 per row, last_slice i32 per slot; lengths and shred_bytes start at 0,
+    last_slice at -1).  slot_ids (host) and slices_per_slot are the window: row = w *
+    slices_per_slot + slice index.  verdict (device u8[n]) gets an INTAKE_* per datagram.
+    Returns (shred_bytes, counts): each row's S_s and occupied slots after the call (numpy)."""
+    import numpy as np
+
+    ids = np.ascontiguousarray(np.asarray(slot_ids, dtype=np.uint64))
+    nrows = ids.size * slices_per_slot
+    sizes = np.zeros(max(nrows, 1), np.uint32)
+    counts = np.zeros(max(nrows, 1), np.uint32)
+    _check(load().ag_shredder_intake_batch(ctx.handle, ids.size, ids.ctypes.data, slices_per_slot, n, _optr(rx),
+                                           rx_stride, _optr(rx_lens), _optr(pk), _optr(packets), packet_stride,
+                                           _optr(packet_lens), _optr(commitments), _optr(shred_bytes),
+                                           _optr(last_slice), _optr(verdict), sizes.ctypes.data, counts.ctypes.data),
+           "ag_shredder_intake_batch")
+    return sizes[:nrows], counts[:nrows]

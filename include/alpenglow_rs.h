@@ -640,6 +640,68 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* ctx, int kind, size_t nslices, siz
                                    uint64_t* slice_indices_out, uint8_t* is_last_out, uint8_t* parent_flags_out,
                                    uint8_t* parent_ids_out, uint32_t* data_offsets_out, uint32_t* data_lens_out);
 
+/* ---- 10. shred intake: received datagrams -> the slice slots of section 9 ----------------
+ * What stands between recvmmsg and ag_shredder_deshred_batch_var for a follower of one leader
+ * (key pk, 32 B, device): n < 2^24 datagrams in ARRIVAL ORDER (device; datagram t at rx + t *
+ * rx_stride, rx_lens[t] bytes, device u32[n]) are validated and routed into a caller-owned
+ * store that persists across calls -- one call per receive batch.
+ *
+ * Window: slot_ids (HOST, nslots >= 1 distinct slots) and slices_per_slot (1 .. 1024).  A
+ * datagram of slot slot_ids[w] and slice index i < slices_per_slot belongs to row r = w *
+ * slices_per_slot + i; nrows = nslots * slices_per_slot < 2^24.
+ * Store (device; initialise lengths and shred_bytes to 0, last_slice to -1):
+ *   packets, packet_stride, packet_lens (u32[64 * nrows]): row r's datagram j in slot 64 r + j,
+ *                      exactly what ag_shredder_deshred_batch_var takes (slots it filled count
+ *                      as occupied);
+ *   commitments        49 B per row: the row's cached SliceCommitment
+ *                      (BlockData::commitment_cache), valid where shred_bytes[r] != 0;
+ *   shred_bytes        u32[nrows]: 0 = no cached commitment yet, else the data length of the
+ *                      shred that set the cache -- the row's S_s;
+ *   last_slice         i32[nslots]: BlockData::last_slice, -1 = none.
+ * Outputs: verdict (device u8[n]); shred_bytes_out / counts_out (HOST u32[nrows], nullable):
+ * each row's S_s and its number of occupied slots after the call -- what the caller passes to
+ * deshred_batch_var and where it sees which rows reached 32.
+ *
+ * verdict[t] is what processing the datagrams one at a time, in order, gives datagram t:
+ *   1. network::deserialize rejects it, its length is 0 (or above rx_stride) -> MALFORMED.
+ *   2. Its slot is not in slot_ids, or its slice index >= slices_per_slot -> OUT_OF_WINDOW.
+ *   3. Its kind does not match its shred index j (Data for j < 32), or its data length is zero,
+ *      odd or above 1024, or its path is not 6 digests -> IMPLAUSIBLE (never stored; the
+ *      deviation from the reference that ag_shredder_deshred_batch documents).
+ *   4. ValidatedShred::try_new (validated_shred.rs:52-79) with the row's cached commitment: no
+ *      cache -- the signature decides (INVALID_SIGNATURE); cache, equal commitment -- accepted
+ *      without a signature check; cache, another commitment -- EQUIVOCATION if its signature
+ *      verifies, else INVALID_SIGNATURE.
+ *   5. Accepted, but its data length is not the row's S_s -> SIZE_MISMATCH (deshred_batch_var
+ *      would count it as absent).
+ *   6. BlockData::add_shred (slot_block_data.rs:214-248): a vacant cache takes this commitment
+ *      and data length (even if the shred is then rejected).  Last slice: none yet and is_last
+ *      set -- marked, and every row of the slot with a higher slice index is pruned (its slot
+ *      lengths become 0, its bytes unspecified, its cache kept; datagrams stored there earlier
+ *      in this call get PRUNED); last slice l known -- the shred must satisfy (i < l && !is_last)
+ *      || (i == l && is_last), else EQUIVOCATION.  Slot (r, j) occupied -> DUPLICATE.  Otherwise
+ *      the datagram is copied to its slot, the slot's length set -> STORED.
+ * The device runs the parallel form of this in a fixed number of launches, at most two of them
+ * signature checks (one signature per row from an honest leader), whatever the datagrams hold.
+ * No byte of a slot past the stored length is written, no slot but the STORED ones (and the
+ * zeroed lengths of pruned rows), and rx never.
+ * Errors (nothing launched, nothing written), all INVALID_ARGUMENT: a null store, window or
+ * ctx pointer, a null rx / rx_lens / pk / verdict with n > 0, nslots = 0, duplicate slot_ids,
+ * slices_per_slot out of range, nrows or n >= 2^24, rx_stride or packet_stride below
+ * ag_shred_datagram_bytes(1024, 6), and rx, packets, rx_stride or packet_stride no multiple of
+ * 16.  n == 0 returns AG_RS_OK and still fills the HOST outputs.  Synchronous. */
+enum {
+  AG_INTAKE_STORED = 0, AG_INTAKE_MALFORMED = 1, AG_INTAKE_OUT_OF_WINDOW = 2, AG_INTAKE_IMPLAUSIBLE = 3,
+  AG_INTAKE_INVALID_SIGNATURE = 4, AG_INTAKE_EQUIVOCATION = 5, AG_INTAKE_SIZE_MISMATCH = 6,
+  AG_INTAKE_DUPLICATE = 7, AG_INTAKE_PRUNED = 8
+};
+int ag_shredder_intake_batch(ag_rs_ctx* ctx, size_t nslots, const uint64_t* slot_ids /* HOST */,
+                             size_t slices_per_slot, size_t n, const uint8_t* rx, size_t rx_stride,
+                             const uint32_t* rx_lens, const uint8_t* pk, uint8_t* packets, size_t packet_stride,
+                             uint32_t* packet_lens, uint8_t* commitments, uint32_t* shred_bytes,
+                             int32_t* last_slice, uint8_t* verdict, uint32_t* shred_bytes_out /* HOST */,
+                             uint32_t* counts_out /* HOST */);
+
 #ifdef __cplusplus
 }
 #endif
