@@ -15,55 +15,12 @@
 #include <cstdint>
 
 #include "intake.hpp"
-#include "unaligned.hpp"
+#include "intake_device.hpp"
 #include "wire.hpp"
 
 namespace ag {
 
 namespace {
-
-enum : uint8_t {  // AG_INTAKE_* (include/alpenglow_rs.h)
-  kStored = 0, kMalformed = 1, kOutOfWindow = 2, kImplausible = 3, kInvalidSignature = 4, kEquivocation = 5,
-  kSizeMismatch = 6, kDuplicate = 7, kPruned = 8
-};
-
-__device__ __forceinline__ void min_index(uint32_t* word, uint32_t t) {
-  if (*static_cast<volatile uint32_t*>(word) > t) atomicMin(word, t);
-}
-
-// SliceCommitment (shredder.rs:206-215): 49 bytes as 12 little-endian words and one byte.
-struct Commit {
-  uint32_t w[12];
-  uint32_t last;
-};
-__device__ __forceinline__ Commit load_commit(const uint8_t* p) {
-  Commit c;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const uint4 x = ld16u(p + 16 * q);
-    c.w[4 * q] = x.x;
-    c.w[4 * q + 1] = x.y;
-    c.w[4 * q + 2] = x.z;
-    c.w[4 * q + 3] = x.w;
-  }
-  c.last = p[48];
-  return c;
-}
-__device__ __forceinline__ void store_commit(uint8_t* p, const Commit& c) {
-#pragma unroll
-  for (int q = 0; q < 3; ++q) st16u(p + 16 * q, make_uint4(c.w[4 * q], c.w[4 * q + 1], c.w[4 * q + 2], c.w[4 * q + 3]));
-  p[48] = static_cast<uint8_t>(c.last);
-}
-__device__ __forceinline__ bool same_commit(const Commit& a, const Commit& b) {
-  uint32_t diff = a.last ^ b.last;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) diff |= a.w[i] ^ b.w[i];
-  return diff == 0;
-}
-
-__device__ __forceinline__ uint32_t meta_index(uint32_t m) { return m & 0xFFu; }
-__device__ __forceinline__ bool meta_last(uint32_t m) { return (m >> 8) & 1u; }
-__device__ __forceinline__ uint32_t meta_len(uint32_t m) { return m >> 16; }
 
 // Is slice index i with flag is_last consistent with the last slice l (slot_block_data.rs:228)?
 __device__ __forceinline__ bool last_consistent(uint32_t i, bool is_last, uint32_t l) {
@@ -121,16 +78,7 @@ __global__ __launch_bounds__(256) void intake_commit_kernel(const IntakeParams p
   const uint4 x = *reinterpret_cast<const uint4*>(p.roots + 32 * t);
   const uint4 y = *reinterpret_cast<const uint4*>(p.roots + 32 * t + 16);
   const uint32_t root[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-  Commit c;
-  c.w[0] = static_cast<uint32_t>(slot);
-  c.w[1] = static_cast<uint32_t>(slot >> 32);
-  c.w[2] = static_cast<uint32_t>(si);
-  c.w[3] = static_cast<uint32_t>(si >> 32);
-  c.w[4] = (meta_last(p.meta[t]) ? 1u : 0u) | (root[0] << 8);
-#pragma unroll
-  for (int k = 1; k < 8; ++k) c.w[4 + k] = __builtin_amdgcn_alignbyte(root[k], root[k - 1], 3);
-  c.last = root[7] >> 24;
-  store_commit(p.commit + kIntakeCommitStride * t, c);
+  store_commit(p.commit + kIntakeCommitStride * t, make_commit(slot, si, meta_last(p.meta[t]), root));
   if (p.pick[r] == t) p.list1[atomicAdd(p.counts, 1u)] = static_cast<uint32_t>(t);
 }
 

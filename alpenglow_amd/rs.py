@@ -86,7 +86,7 @@ EXPORTS = (
     "ag_slice_frame_batch", "ag_slice_parse_batch",
     "ag_shredder_shred_batch", "ag_shredder_deshred_batch", "ag_shredder_shred_batch_var",
     "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind", "ag_shredder_deshred_batch_var",
-    "ag_shredder_intake_batch",
+    "ag_shredder_intake_batch", "ag_repair_intake_batch",
 )
 
 
@@ -183,6 +183,7 @@ def load():
         "ag_shredder_deshred_batch_kind": ([p, i, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
         "ag_shredder_deshred_batch_var": ([p, sz, p, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
         "ag_shredder_intake_batch": ([p, sz, p, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p], i),
+        "ag_repair_intake_batch": ([p, sz, p, p, sz, sz, p, sz, p, p, p, p, p, p, p, sz, p, p, p, p, p, p, p, p], i),
     }
     sigs["ag_rs_internal_last_decode_classes"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_encode_kernels"] = ([p, p], i)  # test aid, not in the header
@@ -1206,6 +1207,9 @@ def shredder_deshred_batch_kind(ctx: Context, kind: int, nslices: int, shred_byt
  INTAKE_EQUIVOCATION, INTAKE_SIZE_MISMATCH, INTAKE_DUPLICATE, INTAKE_PRUNED) = range(9)
 INTAKE_VERDICTS = ("stored", "malformed", "out_of_window", "implausible", "invalid_signature", "equivocation",
                    "size_mismatch", "duplicate", "pruned")
+# ag_repair_intake_batch only
+INTAKE_REQUEST_MISMATCH, INTAKE_NO_ROOT, INTAKE_WRONG_ROOT = 9, 10, 11
+REPAIR_VERDICTS = INTAKE_VERDICTS + ("request_mismatch", "no_root", "wrong_root")
 
 
 def shredder_intake_batch(ctx: Context, slot_ids, slices_per_slot: int, n: int, rx, rx_stride: int, rx_lens, pk,
@@ -1229,4 +1233,33 @@ def shredder_intake_batch(ctx: Context, slot_ids, slices_per_slot: int, n: int, 
                                            _optr(packet_lens), _optr(commitments), _optr(shred_bytes),
                                            _optr(last_slice), _optr(verdict), sizes.ctypes.data, counts.ctypes.data),
            "ag_shredder_intake_batch")
+    return sizes[:nrows], counts[:nrows]
+
+
+def repair_intake_batch(ctx: Context, block_slots, pks, slices_per_block: int, n: int, rx, rx_stride: int, rx_lens,
+                        req_block, req_slice, req_index, slice_roots, have_root, packets, packet_stride: int,
+                        packet_lens, commitments, signatures, shred_bytes, last_slice, verdict):
+    """ag_repair_intake_batch: n repair replies in arrival order (device rx / rx_lens: the Shred of
+    each RepairResponse::Shred), each with the coordinates of the request it answers (device u32
+    req_block / req_slice / req_index), are validated as repair.rs:410-445 does -- header against
+    the request, derived root against the proved slice root (device slice_roots 32 B per row,
+    have_root u8 per row), the signature always, under the block's leader key (device pks, 32 B per
+    block) -- and stored by BlockData::add_shred's rules per repaired block.  block_slots (host;
+    two blocks may share a slot) and slices_per_block give the rows: row = req_block *
+    slices_per_block + req_slice.  The store is shredder_intake_batch's plus signatures (64 B per
+    row) and last_slice per block.  verdict (device u8[n]) gets an INTAKE_* per reply.
+    Returns (shred_bytes, counts): each row's S_s and occupied slots after the call (numpy)."""
+    import numpy as np
+
+    slots = np.ascontiguousarray(np.asarray(block_slots, dtype=np.uint64))
+    nrows = slots.size * slices_per_block
+    sizes = np.zeros(max(nrows, 1), np.uint32)
+    counts = np.zeros(max(nrows, 1), np.uint32)
+    _check(load().ag_repair_intake_batch(ctx.handle, slots.size, slots.ctypes.data, _optr(pks), slices_per_block, n,
+                                         _optr(rx), rx_stride, _optr(rx_lens), _optr(req_block), _optr(req_slice),
+                                         _optr(req_index), _optr(slice_roots), _optr(have_root), _optr(packets),
+                                         packet_stride, _optr(packet_lens), _optr(commitments), _optr(signatures),
+                                         _optr(shred_bytes), _optr(last_slice), _optr(verdict), sizes.ctypes.data,
+                                         counts.ctypes.data),
+           "ag_repair_intake_batch")
     return sizes[:nrows], counts[:nrows]

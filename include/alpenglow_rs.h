@@ -693,7 +693,9 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* ctx, int kind, size_t nslices, siz
 enum {
   AG_INTAKE_STORED = 0, AG_INTAKE_MALFORMED = 1, AG_INTAKE_OUT_OF_WINDOW = 2, AG_INTAKE_IMPLAUSIBLE = 3,
   AG_INTAKE_INVALID_SIGNATURE = 4, AG_INTAKE_EQUIVOCATION = 5, AG_INTAKE_SIZE_MISMATCH = 6,
-  AG_INTAKE_DUPLICATE = 7, AG_INTAKE_PRUNED = 8
+  AG_INTAKE_DUPLICATE = 7, AG_INTAKE_PRUNED = 8,
+  /* section 11 only */
+  AG_INTAKE_REQUEST_MISMATCH = 9, AG_INTAKE_NO_ROOT = 10, AG_INTAKE_WRONG_ROOT = 11
 };
 int ag_shredder_intake_batch(ag_rs_ctx* ctx, size_t nslots, const uint64_t* slot_ids /* HOST */,
                              size_t slices_per_slot, size_t n, const uint8_t* rx, size_t rx_stride,
@@ -701,6 +703,72 @@ int ag_shredder_intake_batch(ag_rs_ctx* ctx, size_t nslots, const uint64_t* slot
                              uint32_t* packet_lens, uint8_t* commitments, uint32_t* shred_bytes,
                              int32_t* last_slice, uint8_t* verdict, uint32_t* shred_bytes_out /* HOST */,
                              uint32_t* counts_out /* HOST */);
+
+/* ---- 11. repair intake: repaired shreds -> the block rows of section 9 -------------------
+ * The RepairResponse::Shred handling of a follower that fell behind (repair.rs:410-445 ->
+ * Blockstore::add_shred_from_repair, blockstore.rs:285-309 -> SlotBlockData::
+ * add_shred_from_repair, slot_block_data.rs:101-113 -> BlockData::add_shred): n < 2^24 replies
+ * in ARRIVAL ORDER, the Shred part of reply t at rx + t * rx_stride, rx_lens[t] bytes.  The host
+ * has parsed the RepairResponse envelope and matched it to its outstanding request
+ * (repair.rs:338-353); that request's coordinates come with the reply: req_block[t] (an index
+ * into the caller's list of blocks under repair), req_slice[t], req_index[t] (device u32[n]).
+ *
+ * Blocks: block_slots (HOST, nblocks >= 1; duplicates allowed: two blocks of one slot with
+ * different hashes are different BlockData, `repaired: BTreeMap<BlockHash, BlockData>`), pks
+ * (device, 32 B per block: the leader of the block's slot), slices_per_block (1 .. 1024).  The
+ * row of reply t is r = req_block[t] * slices_per_block + req_slice[t]; nrows = nblocks *
+ * slices_per_block < 2^24.  slice_roots (device, 32 B per row) and have_root (device u8[nrows]):
+ * the slice root proved for (block, slice) (ag_block_proof_check_batch), valid where have_root[r]
+ * != 0.
+ * Store (device, caller-owned, persists across calls; initialise lengths and shred_bytes to 0,
+ * last_slice to -1): packets / packet_stride / packet_lens, commitments, shred_bytes as section
+ * 10, last_slice i32[nblocks] per BLOCK, and
+ *   signatures         64 B per row: the signature that verified for the row's cached
+ *                      commitment, valid where shred_bytes[r] != 0.  It lets a later call skip
+ *                      re-verifying a byte-identical (commitment, signature) pair.
+ * Outputs as section 10: verdict (device u8[n]), shred_bytes_out / counts_out (HOST u32[nrows],
+ * nullable).  Alignment and stride rules are those of section 10.
+ *
+ * verdict[t] is what processing the replies one at a time, in order, gives reply t:
+ *   1. network::deserialize rejects the shred, its length is 0 (or above rx_stride) -> MALFORMED.
+ *   2. req_block[t] >= nblocks, req_slice[t] >= slices_per_block or req_index[t] >= 64 ->
+ *      OUT_OF_WINDOW.
+ *   3. The header's slot is not block_slots[req_block[t]], or its slice index is not
+ *      req_slice[t], or its shred index is not req_index[t] -> REQUEST_MISMATCH
+ *      (repair.rs:417-423).
+ *   4. The plausibility rule of section 10 (kind against index; data length zero, odd or above
+ *      1024; path not 6 digests) -> IMPLAUSIBLE (the same documented deviation).
+ *   5. have_root[r] == 0 -> NO_ROOT (the reference never issues such a request,
+ *      repair.rs:424-426).  The shred's derived root differs from slice_roots[r] -> WRONG_ROOT,
+ *      with no signature check (repair.rs:428-432).
+ *   6. The signature over the shred's own commitment does not verify under pks[req_block[t]] ->
+ *      INVALID_SIGNATURE.  ValidatedShred::try_new(shred, None, leader_pk) (repair.rs:433-437,
+ *      validated_shred.rs:71-77): there is no equal-commitment shortcut -- a reply with the
+ *      row's commitment and a bad signature, which section 10 stores, is invalid here.
+ *   7. BlockData::add_shred, per block: the row's cache holds another commitment ->
+ *      EQUIVOCATION (slot_block_data.rs:214-217; reachable: the same proved root with is_last
+ *      flipped, both signed by the leader).  The row has a cache and the data length is not its
+ *      S_s -> SIZE_MISMATCH (reachable: a leader that signs a tree over leaves of unequal
+ *      sizes).  A vacant cache takes this commitment, signature and data length.  Then the
+ *      last-slice rule with mark_last_slice pruning (EQUIVOCATION, PRUNED), DUPLICATE, or the copy
+ *      and STORED, all as section 10 step 6 with the block in the slot's place.
+ * The device runs the parallel form in a fixed number of launches, at most two of them signature
+ * checks: one verification per row for an honest block, one more for every reply whose 49 + 64
+ * commitment and signature bytes are not those of a pair already known valid.  No byte of a slot
+ * past the stored length is written, no slot but the STORED ones (and the zeroed lengths of
+ * pruned rows), and rx never.
+ * Errors (nothing launched, nothing written), all INVALID_ARGUMENT: those of section 10 (nblocks
+ * and slices_per_block in the window's place; duplicate block_slots are no error), and a null
+ * pks, slice_roots, have_root or signatures, or a null request column with n > 0.  n == 0
+ * returns AG_RS_OK and still fills the HOST outputs.  Synchronous.  Verdicts: AG_INTAKE_* above,
+ * 0 .. 8 with their section 10 meaning and REQUEST_MISMATCH / NO_ROOT / WRONG_ROOT. */
+int ag_repair_intake_batch(ag_rs_ctx* ctx, size_t nblocks, const uint64_t* block_slots /* HOST */,
+                           const uint8_t* pks, size_t slices_per_block, size_t n, const uint8_t* rx,
+                           size_t rx_stride, const uint32_t* rx_lens, const uint32_t* req_block,
+                           const uint32_t* req_slice, const uint32_t* req_index, const uint8_t* slice_roots,
+                           const uint8_t* have_root, uint8_t* packets, size_t packet_stride, uint32_t* packet_lens,
+                           uint8_t* commitments, uint8_t* signatures, uint32_t* shred_bytes, int32_t* last_slice,
+                           uint8_t* verdict, uint32_t* shred_bytes_out /* HOST */, uint32_t* counts_out /* HOST */);
 
 #ifdef __cplusplus
 }
