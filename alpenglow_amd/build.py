@@ -30,8 +30,8 @@ CXX = os.environ.get("CXX_HOST", "g++")
 
 # one TU per RS kernel family (the slowest to compile first: they set the build's wall time)
 RS_KERNEL_SOURCES = ["rs_tile64.hip", "rs_window.hip", "rs_generic.hip", "rs_coder_kernels.hip"]
-SOURCES = [*RS_KERNEL_SOURCES, "rs_xform64.hip", "rs_decode_c.hip", "rs_var.hip", "merkle.hip", "cipher.hip", "ed25519.hip", "wire.hip", "slice.hip", "shredder.hip", "intake.hip", "repair.hip", "rs_api.cpp", "rs_coder_api.cpp", "crypto_api.cpp", "wire_api.cpp", "rs_dispatch.cpp", "shredder_api.cpp", "intake_api.cpp", "repair_api.cpp", "rs_patterns.cpp", "gf16.cpp"]
-HEADERS = ["gf16.hpp", "rs_device.hpp", "rs_xform.hpp", "rs_xform8.hpp", "rs_decode_pk.hpp", "rs_launch.hpp", "rs_consts.inc", "rs_patterns.hpp", "rs_ctx.hpp", "merkle.hpp", "sha256.hpp", "cipher.hpp", "ed25519.hpp", "ed25519_core.hpp", "wire.hpp", "slice.hpp", "shredder.hpp", "intake.hpp", "intake_device.hpp", "intake_scratch.hpp", "repair.hpp", "unaligned.hpp"]
+SOURCES = [*RS_KERNEL_SOURCES, "rs_xform64.hip", "rs_decode_c.hip", "rs_var.hip", "merkle.hip", "cipher.hip", "ed25519.hip", "wire.hip", "slice.hip", "shredder.hip", "intake.hip", "repair.hip", "block.hip", "rs_api.cpp", "rs_coder_api.cpp", "crypto_api.cpp", "wire_api.cpp", "rs_dispatch.cpp", "shredder_api.cpp", "intake_api.cpp", "repair_api.cpp", "block_api.cpp", "rs_patterns.cpp", "gf16.cpp"]
+HEADERS = ["gf16.hpp", "rs_device.hpp", "rs_xform.hpp", "rs_xform8.hpp", "rs_decode_pk.hpp", "rs_launch.hpp", "rs_consts.inc", "rs_patterns.hpp", "rs_ctx.hpp", "merkle.hpp", "sha256.hpp", "cipher.hpp", "ed25519.hpp", "ed25519_core.hpp", "wire.hpp", "slice.hpp", "shredder.hpp", "intake.hpp", "intake_device.hpp", "intake_scratch.hpp", "repair.hpp", "block.hpp", "unaligned.hpp"]
 # -fno-slp-vectorize: the SLP vectoriser packs the bitsliced XOR networks into <2 x i32>
 # ops, which lengthens live ranges (measured +40 VGPRs on the transform kernel).
 # -amdgpu-promote-alloca-to-vector-limit: keeps the four-Russians tables of decode_x and

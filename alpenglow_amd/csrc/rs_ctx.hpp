@@ -1,6 +1,6 @@
 // The device context behind the C ABI (include/alpenglow_rs.h) and the helpers the host
 // translation units share: rs_api.cpp, rs_coder_api.cpp, crypto_api.cpp and wire_api.cpp (the C
-// ABI), rs_dispatch.cpp (the batch encode / decode dispatch), shredder_api.cpp, intake_api.cpp and repair_api.cpp.  Internal: not
+// ABI), rs_dispatch.cpp (the batch encode / decode dispatch), shredder_api.cpp, intake_api.cpp, repair_api.cpp and block_api.cpp.  Internal: not
 // installed, included only by the host .cpp files; nothing here is exported from the shared object.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -245,6 +245,9 @@ struct ag_rs_ctx {
   DevBuf d_repair;                          // repair intake scratch (repair_api.cpp: intake's layout + key rows)
   StagedUpload repair_blocks;               // its blocks' slot ids (u64), in the caller's order
   PinBuf h_repair;                          // pinned staging of its per-row host outputs
+  DevBuf d_block;                           // block assembly scratch and staged outputs (block_api.cpp carves it up)
+  StagedUpload block_cols;                  // its host columns: data lengths | parent ids | row_ok | parent flags
+  PinBuf h_block;                           // pinned staging of its host outputs
   // host-memory calls: two staging slots, H2D / D2H streams next to the compute stream
   struct Slot {
     DevBuf in, out;

@@ -86,7 +86,7 @@ EXPORTS = (
     "ag_slice_frame_batch", "ag_slice_parse_batch",
     "ag_shredder_shred_batch", "ag_shredder_deshred_batch", "ag_shredder_shred_batch_var",
     "ag_shredder_shred_batch_kind", "ag_shredder_deshred_batch_kind", "ag_shredder_deshred_batch_var",
-    "ag_shredder_intake_batch", "ag_repair_intake_batch",
+    "ag_shredder_intake_batch", "ag_repair_intake_batch", "ag_block_assemble_batch",
 )
 
 
@@ -184,6 +184,8 @@ def load():
         "ag_shredder_deshred_batch_var": ([p, sz, p, p, sz, p, p, p, sz, p, p, p, p, p, p, p, p], i),
         "ag_shredder_intake_batch": ([p, sz, p, sz, sz, p, sz, p, p, p, sz, p, p, p, p, p, p, p], i),
         "ag_repair_intake_batch": ([p, sz, p, p, sz, sz, p, sz, p, p, p, p, p, p, p, sz, p, p, p, p, p, p, p, p], i),
+        "ag_block_assemble_batch": ([p, sz, sz, p, p, p, p, p, p, sz, p, sz, p, sz, p, p, p, p, p, p, p, p, sz, p, sz,
+                                     p, p, sz, p, p], i),
     }
     sigs["ag_rs_internal_last_decode_classes"] = ([p, p], i)  # test aid, not in the header
     sigs["ag_rs_internal_last_encode_kernels"] = ([p, p], i)  # test aid, not in the header
@@ -1263,3 +1265,76 @@ def repair_intake_batch(ctx: Context, block_slots, pks, slices_per_block: int, n
                                          counts.ctypes.data),
            "ag_repair_intake_batch")
     return sizes[:nrows], counts[:nrows]
+
+
+# ---- block assembly: reconstructed slices -> blocks (slot_block_data.rs:376-454) --------------
+
+BLOCK_INCOMPLETE, BLOCK_COMPLETE, BLOCK_PARENT_SAME, BLOCK_PARENT_TWICE, BLOCK_BAD_TRANSACTIONS = range(5)
+BLOCK_VERDICTS = ("incomplete", "complete", "parent_same", "parent_twice", "bad_transactions")
+BLOCK_MAX_TXS_PER_SLICE = 1365  # AG_BLOCK_MAX_TXS_PER_SLICE: wincode's preallocation limit as recalled (unpinned)
+
+
+@dataclass
+class BlockAssembly:
+    """Per-block results of block_assemble_batch (numpy arrays).  verdict[b] is a BLOCK_*;
+    error_slice[b] the slice a failed block failed at; parents[b] None or (slot, hash bytes),
+    the parent of a COMPLETE block; tx_counts / tx_bytes / tx_first index the transaction table;
+    hashes (nblocks, 32): the host copy of the block hashes (rows of INCOMPLETE blocks zero)."""
+    verdict: object
+    error_slice: object
+    parents: list
+    tx_counts: object
+    tx_bytes: object
+    tx_first: object
+    tx_total: int
+    hashes: object
+
+
+def block_assemble_batch(ctx: Context, nblocks: int, slices_per_block: int, row_ok, parents, data_offsets, data_lens,
+                         codewords, codeword_stride: int, slice_roots, roots_stride: int, last_slice, block_hashes,
+                         max_txs_per_slice: int = BLOCK_MAX_TXS_PER_SLICE, nodes=None, nodes_stride: int = 0,
+                         proofs=None, proofs_stride: int = 0, tx_offsets=None, tx_lens=None,
+                         tx_capacity: int = 0) -> BlockAssembly:
+    """ag_block_assemble_batch: BlockData::try_reconstruct_block for nblocks blocks of
+    slices_per_block rows (row = block * slices_per_block + slice index) whose payloads the
+    deshred left in codewords (device).  row_ok, parents, data_offsets, data_lens: host, one per
+    row, as ``DeshredBatch`` has them (row_ok = status == 0; parents a list of None or (slot,
+    hash), or the (flags, ids) arrays).  slice_roots / roots_stride (device): e.g. the stores'
+    commitments + 17 with stride 49; last_slice (device i32 per block): the stores'.
+    block_hashes (device, 32 B per block), nodes / proofs (device, optional) as block_tree_batch.
+    tx_offsets (u64) / tx_lens (u32) (device, optional, tx_capacity entries): the transaction
+    table, written only when the total fits."""
+    import numpy as np
+
+    nrows = nblocks * slices_per_block
+    if isinstance(parents, tuple) and len(parents) == 2 and hasattr(parents[0], "dtype"):
+        flags = np.ascontiguousarray(parents[0], dtype=np.uint8)
+        ids = np.ascontiguousarray(parents[1], dtype=np.uint8)
+        if flags.size != nrows or ids.size != BLOCK_ID_BYTES * nrows:
+            raise ValueError("parents do not match the batch")
+    else:
+        flags, ids = _parent_arrays(parents, nrows)
+    ok = np.ascontiguousarray(np.asarray(row_ok, dtype=np.uint8))
+    if ok.size != nrows:
+        raise ValueError("row_ok does not match the batch")
+    offs, lens = _u32(data_offsets, nrows), _u32(data_lens, nrows)
+    nb = max(nblocks, 1)
+    verdict = np.zeros(nb, np.uint8)
+    err = np.zeros(nb, np.uint32)
+    par = np.zeros((nb, BLOCK_ID_BYTES), np.uint8)
+    txc = np.zeros(nb, np.uint32)
+    txb = np.zeros(nb, np.uint64)
+    first = np.zeros(nb, np.uint64)
+    total = np.zeros(1, np.uint64)
+    hashes = np.zeros((nb, 32), np.uint8)
+    _check(load().ag_block_assemble_batch(ctx.handle, nblocks, slices_per_block, ok.ctypes.data, flags.ctypes.data,
+                                          ids.ctypes.data, offs.ctypes.data, lens.ctypes.data, _optr(codewords),
+                                          codeword_stride, _optr(slice_roots), roots_stride, _optr(last_slice),
+                                          max_txs_per_slice, verdict.ctypes.data, err.ctypes.data, par.ctypes.data,
+                                          txc.ctypes.data, txb.ctypes.data, _optr(block_hashes), hashes.ctypes.data,
+                                          _optr(nodes), nodes_stride, _optr(proofs), proofs_stride, _optr(tx_offsets),
+                                          _optr(tx_lens), tx_capacity, first.ctypes.data, total.ctypes.data),
+           "ag_block_assemble_batch")
+    parent_list = _parent_list(verdict[:nblocks] == BLOCK_COMPLETE, par)
+    return BlockAssembly(verdict[:nblocks], err[:nblocks], parent_list, txc[:nblocks], txb[:nblocks],
+                         first[:nblocks], int(total[0]), hashes[:nblocks])

@@ -770,6 +770,81 @@ int ag_repair_intake_batch(ag_rs_ctx* ctx, size_t nblocks, const uint64_t* block
                            uint8_t* commitments, uint8_t* signatures, uint32_t* shred_bytes, int32_t* last_slice,
                            uint8_t* verdict, uint32_t* shred_bytes_out /* HOST */, uint32_t* counts_out /* HOST */);
 
+/* ---- 12. block assembly: reconstructed slices -> blocks -----------------------------------
+ * BlockData::try_reconstruct_block (slot_block_data.rs:376-454) for nblocks blocks whose slices
+ * sit where sections 10 / 11 and ag_shredder_deshred_batch_var left them: block b, slice i is row
+ * r = b * slices_per_block + i (nrows = nblocks * slices_per_block < 2^24), its framed payload at
+ * codewords + r * codeword_stride (device, 16-byte aligned, stride % 16 == 0 and >= 32768).
+ * Per row (HOST, as the deshred calls return them): row_ok (non-zero: the row's slice is in
+ * BlockData::slices, deshred status 0), parent_flags / parent_ids (40 B per row), data_offsets
+ * (9 without a parent, 49 with one) / data_lens.  slice_roots (device): row r's root at
+ * slice_roots + r * roots_stride, any stride >= 32 and no alignment -- the stores' commitments +
+ * 17 with stride 49 as they are.  last_slice (device i32[nblocks]): the stores'.
+ *
+ * Per block, the first rule that applies gives verdict_out[b]:
+ *   1. INCOMPLETE (ReconstructBlockResult::NoAction): l = last_slice[b] is negative or >=
+ *      slices_per_block; or some row 0 ..= l has row_ok == 0; or row 0 carries no parent
+ *      (try_reconstruct_slice never inserts such a slice, :361-364).  Rows above l are ignored.
+ *   2. Otherwise the block hash is DoubleMerkleTree::new(slice roots 0 ..= l).get_root(); it
+ *      (and the optional nodes and proofs, laid out as ag_block_tree_batch lays them out) is
+ *      written for every block that is not INCOMPLETE, the failed ones included (:390-394).
+ *   3. The slices in index order, parent starting as slice 0's (:401-436).  Slice i > 0 with a
+ *      parent p: p == parent (all 40 bytes) -> PARENT_SAME at i; else a switch has already
+ *      happened -> PARENT_TWICE at i; else parent = p.
+ *   4. Then, for slice i (slice 0 too), deserialize_exact::<Vec<Transaction>> over its data_lens
+ *      bytes: a u64 LE count n, then n times a u64 LE length and that many bytes, exactly
+ *      data_lens bytes consumed.  Fewer than 8 bytes, a length prefix that does not fit, a length
+ *      above the bytes left (compared without overflow), trailing bytes, or n >
+ *      max_txs_per_slice when that is non-zero -> BAD_TRANSACTIONS at i.
+ *   5. No slice failed: COMPLETE, parents_out[b] = the final parent.
+ * The first failing slice decides, the parent rule before the decode within a slice;
+ * error_slice_out[b] names it (0 for COMPLETE and INCOMPLETE).  parents_out, tx_counts_out (the
+ * block's transactions) and tx_bytes_out (their payload bytes) are zero unless COMPLETE.
+ * block_hashes (device, 32 B per block) / block_hashes_host (HOST copy, nullable): bytes of an
+ * INCOMPLETE block are not written.
+ *
+ * Transaction table (tx_offsets u64 / tx_lens u32, device, tx_capacity entries each, nullable
+ * together): the transactions stay in place.  Transaction q of a COMPLETE block b is entry
+ * tx_first_out[b] + q: its payload is tx_lens[e] bytes at codewords + tx_offsets[e].
+ * tx_first_out is the exclusive prefix sum of tx_counts_out over the blocks in order,
+ * tx_total_out[0] the total.  The table is written if and only if the total <= tx_capacity;
+ * otherwise no entry is written and the call still returns AG_RS_OK with every other output (the
+ * caller reads the total and calls again).  Entries at or past the total are never written.
+ * Nothing else is written; codewords never.  The number of launches does not depend on what the
+ * slices hold, and whether the table fits is decided on the device.
+ *
+ * Errors (nothing launched, nothing written), all INVALID_ARGUMENT: a null ctx; with nblocks > 0
+ * a null pointer other than block_hashes_host, nodes, proofs, tx_offsets and tx_lens;
+ * slices_per_block outside 1 .. 1024; nrows >= 2^24; codewords or codeword_stride no multiple of
+ * 16, or the stride below 32768; roots_stride < 32; block_hashes, nodes, proofs or their strides
+ * no multiple of 16; nodes_stride < 32 * ag_merkle_node_count(slices_per_block) or proofs_stride
+ * < 32 * ag_merkle_height(slices_per_block) * slices_per_block; proofs without nodes; exactly
+ * one of tx_offsets / tx_lens null; a row with row_ok set whose parent flag is above 1, whose
+ * data_offsets is not 9 (flag 0) / 49 (flag 1), or whose data_offsets + data_lens >
+ * AG_SLICE_MAX_DATA.  nblocks == 0 returns AG_RS_OK (tx_total_out[0] = 0 if given).  Synchronous. */
+enum {
+  AG_BLOCK_INCOMPLETE = 0, AG_BLOCK_COMPLETE = 1, AG_BLOCK_PARENT_SAME = 2, AG_BLOCK_PARENT_TWICE = 3,
+  AG_BLOCK_BAD_TRANSACTIONS = 4
+};
+/* wincode's preallocation limit restated for Vec<Transaction>: the reference decodes with
+ * with_preallocation_size_limit::<MAX_DATA_PER_SLICE> (slot_block_data.rs:426-427), and wincode
+ * 0.6 -- as recalled; its source is not vendored, so this value is UNPINNED -- refuses a Vec of
+ * n elements when n * size_of::<Transaction>() (24 bytes) exceeds the limit: n <= 32767 / 24.
+ * Pass it as max_txs_per_slice; 0 means no limit. */
+#define AG_BLOCK_MAX_TXS_PER_SLICE 1365
+int ag_block_assemble_batch(ag_rs_ctx* ctx, size_t nblocks, size_t slices_per_block,
+                            const uint8_t* row_ok /* HOST */, const uint8_t* parent_flags /* HOST */,
+                            const uint8_t* parent_ids /* HOST */, const uint32_t* data_offsets /* HOST */,
+                            const uint32_t* data_lens /* HOST */, const uint8_t* codewords, size_t codeword_stride,
+                            const uint8_t* slice_roots, size_t roots_stride, const int32_t* last_slice,
+                            size_t max_txs_per_slice, uint8_t* verdict_out /* HOST */,
+                            uint32_t* error_slice_out /* HOST */, uint8_t* parents_out /* HOST */,
+                            uint32_t* tx_counts_out /* HOST */, uint64_t* tx_bytes_out /* HOST */,
+                            uint8_t* block_hashes, uint8_t* block_hashes_host /* HOST */, uint8_t* nodes,
+                            size_t nodes_stride, uint8_t* proofs, size_t proofs_stride, uint64_t* tx_offsets,
+                            uint32_t* tx_lens, size_t tx_capacity, uint64_t* tx_first_out /* HOST */,
+                            uint64_t* tx_total_out /* HOST */);
+
 #ifdef __cplusplus
 }
 #endif
