@@ -149,20 +149,15 @@ int ag_block_assemble_batch(ag_rs_ctx* c, size_t nblocks, size_t slices_per_bloc
 
   // The tree (a chain of up to 10 dependent levels per block) and the walk (a chain of dependent
   // loads per row) read only what the scan wrote: the walk runs on the side stream beside the
-  // tree.  An error in between waits for the side stream before it returns.
+  // tree.
   hipStream_t q = c->stream;
-  if ((st = c->ensure_side_stream())) return st;
   AG_HIP(ag::launch_block_scan(p, q));
-  AG_HIP(hipEventRecord(c->side_fork, q));
-  const bool forked = hipStreamWaitEvent(c->side, c->side_fork, 0) == hipSuccess &&
-                      ag::launch_block_walk(p, c->side) == hipSuccess &&
-                      hipEventRecord(c->side_join, c->side) == hipSuccess &&
-                      ag::launch_block_tree(t, q) == hipSuccess &&
-                      hipStreamWaitEvent(q, c->side_join, 0) == hipSuccess;
-  if (!forked) {
-    (void)hipStreamSynchronize(c->side);
-    return AG_RS_ERR_DEVICE;
-  }
+  SideScope side(c);
+  if ((st = side.open())) return st;
+  AG_HIP(ag::launch_block_walk(p, side.stream()));
+  if ((st = side.close())) return st;
+  AG_HIP(ag::launch_block_tree(t, q));
+  if ((st = side.join())) return st;
   AG_HIP(ag::launch_block_finish(p, q));
   AG_HIP(ag::launch_block_total(p, q));
   if (tx_offsets) AG_HIP(ag::launch_block_index(p, q));

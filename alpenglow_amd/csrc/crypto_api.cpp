@@ -113,27 +113,16 @@ int aon_batch(ag_rs_ctx* c, size_t n, uint8_t* buffers, size_t stride, const uin
 
 // ag_shred_validate_batch with the cache entries shared by cached_group consecutive shreds
 // (the composed deshred: one cached commitment per slice).
-int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data_stride, size_t data_bytes,
-                        const uint32_t* shred_index, const uint8_t* proofs, size_t proofs_stride, size_t height,
-                        const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
-                        const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
-                        const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
-                        uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes, size_t leaf_nodes_stride,
-                        uint32_t leaves_per_tree, size_t group_stride, uint32_t skip_row, bool roots_ready,
-                        const uint32_t* leaf_sizes, uint32_t size_group) {
-  // leaf_sizes / size_group (device, nullable): one shred size per size_group consecutive shreds
-  // (MerkleVerifyParams; data_bytes then only bounds the sizes).
-  // roots_ready: step 1 already ran (launch_derive_roots, e.g. on another stream): roots_out holds
-  // every active shred's derived root
+// `merkle`: the shreds and their Merkle paths (step 1's launch; n shreds, `active` nullable);
+// its roots_out and list are filled in here.  The caller has checked its arguments.
+// roots_ready: step 1 already ran (launch_merkle_verify over `merkle`, e.g. on another stream):
+// roots_out holds every active shred's derived root.
+int shred_validate_impl(ag_rs_ctx* c, const ag::MerkleVerifyParams& merkle, const uint64_t* slots,
+                        const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* sigs, size_t sig_stride,
+                        const uint8_t* pk, const uint8_t* cached, const uint8_t* has_cached, uint32_t cached_group,
+                        uint8_t* status, uint8_t* roots_out, uint8_t* commitments_out, bool roots_ready) {
   if (roots_ready && !roots_out) return AG_RS_ERR_INVALID_ARGUMENT;
-  if (!c || n >= kMaxSigBatch || data_bytes >= (size_t{1} << 28) ||
-      height > static_cast<size_t>(ag::kMerkleMaxHeight) ||
-      (n && (!shred_index || !slots || !slice_indices || !is_last || !sigs || !pk || !status ||
-             (data_bytes && !data) || (height && !proofs))) ||
-      (cached == nullptr) != (has_cached == nullptr) || proofs_stride % 16 ||
-      reinterpret_cast<uintptr_t>(proofs) % 16 || (n > 1 && data_stride < data_bytes))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (n == 0) return AG_RS_OK;
+  const size_t n = merkle.n;
   if (c->enter()) return AG_RS_ERR_DEVICE;
   int st = ensure_ed_base(c);
   if (st) return st;
@@ -151,25 +140,9 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
   uint32_t* list = c->d_sh_list.as<uint32_t>();
   uint32_t* count = list + n;
   // 1. Shred::slice_root (shredder.rs:168-175): derive_root from the Merkle path
-  ag::MerkleVerifyParams mp{};
-  mp.leaves = data;
-  mp.leaf_stride = data_stride;
-  mp.leaf_bytes = static_cast<uint32_t>(data_bytes);
-  mp.height = static_cast<uint32_t>(height);
-  mp.index = shred_index;
-  mp.proofs = proofs;
-  mp.proofs_stride = proofs_stride;
-  mp.n = n;
+  ag::MerkleVerifyParams mp = merkle;
   mp.roots_out = roots;
-  mp.active = active;
   mp.list = list;  // scratch until the signature list below reuses it (stream order)
-  mp.leaf_nodes = leaf_nodes;  // the leaf digests for a later Merkle rebuild over the same rows
-  mp.leaf_nodes_stride = leaf_nodes_stride;
-  mp.leaves_per_tree = leaves_per_tree;
-  mp.group_stride = group_stride;
-  mp.skip_row = skip_row;
-  mp.leaf_sizes = leaf_sizes;
-  mp.size_group = size_group;
   if (!roots_ready && ag::launch_merkle_verify(mp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   // 2. SliceCommitment + cached-commitment rule (validated_shred.rs:57-64)
   AG_HIP(hipMemsetAsync(count, 0, 4, c->stream));
@@ -181,7 +154,7 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
   cp.cached = cached;
   cp.has_cached = has_cached;
   cp.cached_group = cached_group;
-  cp.active = active;
+  cp.active = merkle.active;
   cp.n = n;
   cp.commitments = commits;
   cp.status = status;
@@ -205,6 +178,60 @@ int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data
   vp.on_valid = c->d_sh_onvalid.as<uint8_t>();
   vp.base_table = c->d_ed_base.as<int32_t>();
   return ag::launch_ed25519_verify(vp, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+}
+
+// ag_slice_sign_batch in two pieces, so that a caller can sign on another stream than c->stream.
+// The first: the argument checks, the Ed25519 table and the scratch, everything that may launch,
+// wait or free on c->stream (the validation above shares that scratch on that stream).
+int slice_sign_prepare(ag_rs_ctx* c, size_t nslices, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
+                       const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots,
+                       const uint8_t* sigs, const uint8_t* commitments_out) {
+  if (!c || nslices >= kMaxSigBatch ||
+      (nslices && (!seed || !pk || !slots || !slice_indices || !is_last || !roots || !sigs)))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (nslices == 0) return AG_RS_OK;
+  if (c->enter()) return AG_RS_ERR_DEVICE;
+  int st = ensure_ed_base(c);
+  if (st) return st;
+  if (!commitments_out && (st = c->d_sh_commit.ensure(ag::kSliceCommitmentLen * nslices, c->stream))) return st;
+  if ((st = c->d_sh_onvalid.ensure(2 * nslices, c->stream))) return st;
+  return c->d_sh_list.ensure(4 * (nslices + 1), c->stream);
+}
+
+// The second (nslices > 0, prepared): only enqueues, on `stream`.
+int slice_sign_enqueue(ag_rs_ctx* c, size_t nslices, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
+                       const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs,
+                       uint8_t* commitments_out, hipStream_t stream) {
+  const size_t n = nslices;
+  uint8_t* commits = commitments_out ? commitments_out : c->d_sh_commit.as<uint8_t>();
+  uint32_t* list = c->d_sh_list.as<uint32_t>();
+  AG_HIP(hipMemsetAsync(list + n, 0, 4, stream));
+  // SliceCommitment::new (shredder.rs:206-215); no cache, so every slice is listed
+  ag::ShredCommitParams cp{};
+  cp.slots = slots;
+  cp.slice_indices = slice_indices;
+  cp.is_last = is_last;
+  cp.roots = roots;
+  cp.n = n;
+  cp.commitments = commits;
+  cp.status = c->d_sh_onvalid.as<uint8_t>() + n;
+  cp.on_valid = c->d_sh_onvalid.as<uint8_t>();
+  cp.list = list;
+  cp.list_count = list + n;
+  if (ag::launch_shred_commit(cp, stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  // sk.sign_bytes(commitment) (shredder.rs:540)
+  ag::EdSignParams p{};
+  p.seeds = seed;
+  p.seed_stride = 0;
+  p.pks = pk;
+  p.pk_stride = 0;
+  p.msgs = commits;
+  p.msg_stride = ag::kSliceCommitmentLen;
+  p.msg_len = ag::kSliceCommitmentLen;
+  p.sigs = sigs;
+  p.n = n;
+  p.base_table = c->d_ed_base.as<int32_t>();
+  return ag::launch_ed25519_sign(p, stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
 }
 }  // namespace ag::host
 
@@ -550,57 +577,34 @@ int ag_shred_validate_batch(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t 
                             const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
                             const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
                             const uint8_t* has_cached, uint8_t* status, uint8_t* roots_out, uint8_t* commitments_out) {
-  return shred_validate_impl(c, n, data, data_stride, data_bytes, shred_index, proofs, proofs_stride, height, slots,
-                             slice_indices, is_last, sigs, sig_stride, pk, cached, has_cached, 1, nullptr, status,
-                             roots_out, commitments_out);
+  if (!c || n >= kMaxSigBatch || data_bytes >= (size_t{1} << 28) ||
+      height > static_cast<size_t>(ag::kMerkleMaxHeight) ||
+      (n && (!shred_index || !slots || !slice_indices || !is_last || !sigs || !pk || !status ||
+             (data_bytes && !data) || (height && !proofs))) ||
+      (cached == nullptr) != (has_cached == nullptr) || proofs_stride % 16 ||
+      reinterpret_cast<uintptr_t>(proofs) % 16 || (n > 1 && data_stride < data_bytes))
+    return AG_RS_ERR_INVALID_ARGUMENT;
+  if (n == 0) return AG_RS_OK;
+  ag::MerkleVerifyParams mp{};
+  mp.leaves = data;
+  mp.leaf_stride = data_stride;
+  mp.leaf_bytes = static_cast<uint32_t>(data_bytes);
+  mp.height = static_cast<uint32_t>(height);
+  mp.index = shred_index;
+  mp.proofs = proofs;
+  mp.proofs_stride = proofs_stride;
+  mp.n = n;
+  return shred_validate_impl(c, mp, slots, slice_indices, is_last, sigs, sig_stride, pk, cached, has_cached, 1, status,
+                             roots_out, commitments_out, false);
 }
 
 int ag_slice_sign_batch(ag_rs_ctx* c, size_t nslices, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
                         const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs,
                         uint8_t* commitments_out) {
-  if (!c || nslices >= kMaxSigBatch ||
-      (nslices && (!seed || !pk || !slots || !slice_indices || !is_last || !roots || !sigs)))
-    return AG_RS_ERR_INVALID_ARGUMENT;
-  if (nslices == 0) return AG_RS_OK;
-  if (c->enter()) return AG_RS_ERR_DEVICE;
-  int st = ensure_ed_base(c);
-  if (st) return st;
-  uint8_t* commits = commitments_out;
-  if (!commits) {
-    if ((st = c->d_sh_commit.ensure(ag::kSliceCommitmentLen * nslices, c->stream))) return st;
-    commits = c->d_sh_commit.as<uint8_t>();
-  }
-  const size_t n = nslices;
-  if ((st = c->d_sh_onvalid.ensure(2 * n, c->stream)) || (st = c->d_sh_list.ensure(4 * (n + 1), c->stream)))
-    return st;
-  uint32_t* list = c->d_sh_list.as<uint32_t>();
-  AG_HIP(hipMemsetAsync(list + n, 0, 4, c->stream));
-  // SliceCommitment::new (shredder.rs:206-215); no cache, so every slice is listed
-  ag::ShredCommitParams cp{};
-  cp.slots = slots;
-  cp.slice_indices = slice_indices;
-  cp.is_last = is_last;
-  cp.roots = roots;
-  cp.n = n;
-  cp.commitments = commits;
-  cp.status = c->d_sh_onvalid.as<uint8_t>() + n;
-  cp.on_valid = c->d_sh_onvalid.as<uint8_t>();
-  cp.list = list;
-  cp.list_count = list + n;
-  if (ag::launch_shred_commit(cp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  // sk.sign_bytes(commitment) (shredder.rs:540)
-  ag::EdSignParams p{};
-  p.seeds = seed;
-  p.seed_stride = 0;
-  p.pks = pk;
-  p.pk_stride = 0;
-  p.msgs = commits;
-  p.msg_stride = ag::kSliceCommitmentLen;
-  p.msg_len = ag::kSliceCommitmentLen;
-  p.sigs = sigs;
-  p.n = n;
-  p.base_table = c->d_ed_base.as<int32_t>();
-  return ag::launch_ed25519_sign(p, c->stream) == hipSuccess ? AG_RS_OK : AG_RS_ERR_DEVICE;
+  const int st = slice_sign_prepare(c, nslices, seed, pk, slots, slice_indices, is_last, roots, sigs, commitments_out);
+  if (st || nslices == 0) return st;
+  return slice_sign_enqueue(c, nslices, seed, pk, slots, slice_indices, is_last, roots, sigs, commitments_out,
+                            c->stream);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 #include "../../include/alpenglow_rs.h"
 #include "cipher.hpp"
 #include "gf16.hpp"
+#include "merkle.hpp"
 #include "rs_launch.hpp"
 
 #define AG_HIP(expr)                                  \
@@ -221,8 +222,9 @@ struct ag_rs_ctx {
   StagedUpload block_meta;                  // block trees: first[nblocks] (u64), then count[nblocks] (u32)
   DevBuf d_aon_lens, d_aon_digests, d_aon_keys;  // all-or-nothing transforms
   DevBuf d_aon_lens2;                            // the side stream's SHA-256 lengths (AONT deshred)
-  hipStream_t side = nullptr;                    // a second compute stream (AONT deshred's SHA-256)
+  hipStream_t side = nullptr;                    // a second compute stream: used through SideScope only
   hipEvent_t side_fork = nullptr, side_join = nullptr;
+  bool side_open = false;                        // a SideScope is open (they share the events: no nesting)
   DevBuf d_slice_meta;                           // slice framing / parsing metadata
   DevBuf stage_pad;                              // restrided shards (sizes not whole 64-byte chunks)
   StagedUpload lens;                        // coder shred batches: payload lengths (var: | sizes | column prefix)
@@ -384,6 +386,54 @@ struct ag_rs_ctx {
   }
 };
 
+// Work on the context's side stream beside its main stream, and the one rule that goes with it: a
+// call never returns while the side stream still runs work it enqueued, since that work reads and
+// writes buffers the caller gets back.  open() forks the side stream from the main stream's
+// current point, the launches in between go to stream(), close() marks their end and join() makes
+// the main stream wait for it.  A scope destroyed between open() and join() -- any error return
+// in between, written as a plain `return st;` -- waits for the side stream on the host.  The
+// context's two events are shared, so scopes do not nest.  Nothing else touches c->side,
+// side_fork or side_join.
+namespace ag {
+namespace host __attribute__((visibility("hidden"))) {
+class SideScope {
+ public:
+  explicit SideScope(ag_rs_ctx* c) : c_(c) {}
+  SideScope(const SideScope&) = delete;
+  SideScope& operator=(const SideScope&) = delete;
+  ~SideScope() {
+    if (!open_) return;
+    (void)hipStreamSynchronize(c_->side);
+    c_->side_open = false;
+  }
+  int open() {
+    if (c_->side_open) return AG_RS_ERR_DEVICE;
+    const int st = c_->ensure_side_stream();
+    if (st) return st;
+    AG_HIP(hipEventRecord(c_->side_fork, c_->stream));
+    AG_HIP(hipStreamWaitEvent(c_->side, c_->side_fork, 0));
+    c_->side_open = open_ = true;
+    return AG_RS_OK;
+  }
+  bool is_open() const { return open_; }
+  hipStream_t stream() const { return c_->side; }
+  int close() {
+    AG_HIP(hipEventRecord(c_->side_join, c_->side));
+    return AG_RS_OK;
+  }
+  int join() {
+    AG_HIP(hipStreamWaitEvent(c_->stream, c_->side_join, 0));
+    c_->side_open = open_ = false;
+    return AG_RS_OK;
+  }
+
+ private:
+  ag_rs_ctx* c_;
+  bool open_ = false;
+};
+}  // namespace host
+}  // namespace ag
+
 // =====================================================================================
 // Crate API mirror: ReedSolomonEncoder / ReedSolomonDecoder (one codeword, host memory)
 // =====================================================================================
@@ -470,15 +520,16 @@ int merkle_var_launch(ag_rs_ctx* c, size_t nslices, const uint32_t* d_sizes, con
                       size_t proofs_stride);
 int aon_batch(ag_rs_ctx* c, size_t n, uint8_t* buffers, size_t stride, const uint32_t* lens, uint32_t extra,
               ag::BufferBatch* bb);
-int shred_validate_impl(ag_rs_ctx* c, size_t n, const uint8_t* data, size_t data_stride, size_t data_bytes,
-                        const uint32_t* shred_index, const uint8_t* proofs, size_t proofs_stride, size_t height,
-                        const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
-                        const uint8_t* sigs, size_t sig_stride, const uint8_t* pk, const uint8_t* cached,
-                        const uint8_t* has_cached, uint32_t cached_group, const uint8_t* active, uint8_t* status,
-                        uint8_t* roots_out, uint8_t* commitments_out, uint8_t* leaf_nodes = nullptr,
-                        size_t leaf_nodes_stride = 0, uint32_t leaves_per_tree = 0, size_t group_stride = 0,
-                        uint32_t skip_row = 0, bool roots_ready = false, const uint32_t* leaf_sizes = nullptr,
-                        uint32_t size_group = 0);
+int shred_validate_impl(ag_rs_ctx* c, const ag::MerkleVerifyParams& merkle, const uint64_t* slots,
+                        const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* sigs, size_t sig_stride,
+                        const uint8_t* pk, const uint8_t* cached, const uint8_t* has_cached, uint32_t cached_group,
+                        uint8_t* status, uint8_t* roots_out, uint8_t* commitments_out, bool roots_ready);
+int slice_sign_prepare(ag_rs_ctx* c, size_t nslices, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
+                       const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots,
+                       const uint8_t* sigs, const uint8_t* commitments_out);
+int slice_sign_enqueue(ag_rs_ctx* c, size_t nslices, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
+                       const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs,
+                       uint8_t* commitments_out, hipStream_t stream);
 
 }  // namespace host
 }  // namespace ag

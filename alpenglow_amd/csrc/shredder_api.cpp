@@ -7,13 +7,11 @@
 //
 // The entry points keep what is their own (argument checks, framing, the coder call, how a
 // failed slice is decoded again) and share the stages around it: the row layout as data
-// (ShredderKind), shred_tail, deshred_front, pipe_statuses, fill_missing.  Side-stream rule:
-// every error return between recording side_fork and waiting on side_join drains c->side first
-// (drain_side), so a failed call never leaves work running on buffers its caller gets back.
+// (ShredderKind), shred_tail, deshred_front, pipe_statuses, fill_missing.  Work on the context's side
+// stream goes through SideScope (rs_ctx.hpp), which states and keeps the side-stream rule.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <utility>
 #include <vector>
 
 #include "../../include/alpenglow_rs.h"
@@ -36,8 +34,8 @@ constexpr size_t kPipeProofBytes = 32 * ag::kPipeHeight;  // one Merkle path of 
 // shred side uses the per-shred columns it writes and the two per-slice buffers at the end.
 // No two roles share a buffer.  One role has two users in the Regular deshred: kBufMerkleList
 // is the compaction list of the proof verify (side stream) and then of the Merkle rebuild (main
-// stream) -- safe because the main stream waits on side_join before the second validation, long
-// before the rebuild is enqueued.
+// stream) -- safe because the main stream joins the side stream before the second validation,
+// long before the rebuild is enqueued.
 enum PipeBuf : int {
   // per shred (N = 64 n rows): the ShredColumns of both sides
   kBufKind,
@@ -90,12 +88,6 @@ int pipe_buf(ag_rs_ctx* c, PipeBuf i, size_t bytes, uint8_t** out) {
   if (st) return st;
   *out = c->pipe[i].as<uint8_t>();
   return AG_RS_OK;
-}
-
-// The side-stream rule's error return: wait for what the side stream still runs, then fail.
-int drain_side(ag_rs_ctx* c, int st) {
-  if (c->side) (void)hipStreamSynchronize(c->side);
-  return st;
 }
 
 // The per-slice columns pipe_check writes (present | slot | slice index | is_last, contiguous
@@ -185,28 +177,12 @@ int kind_merkle(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const u
              : AG_RS_ERR_DEVICE;
 }
 
-// ag_slice_sign_batch on the context's side stream, forked from the main stream's current point
-// (the roots): the signing (one signature per lane, latency-bound) overlaps the serialization of
-// everything else in the datagrams; the caller waits on side_join before it patches the
-// signatures in.
-int sign_on_side(ag_rs_ctx* c, size_t n, const uint8_t* seed, const uint8_t* pk, const uint64_t* slots,
-                 const uint64_t* slice_indices, const uint8_t* is_last, const uint8_t* roots, uint8_t* sigs) {
-  int st;
-  if ((st = c->ensure_side_stream())) return st;
-  AG_HIP(hipEventRecord(c->side_fork, c->stream));
-  if (hipStreamWaitEvent(c->side, c->side_fork, 0) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
-  std::swap(c->stream, c->side);
-  st = ag_slice_sign_batch(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs, nullptr);
-  std::swap(c->stream, c->side);
-  if (st) return drain_side(c, st);
-  if (hipEventRecord(c->side_join, c->side) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
-  return AG_RS_OK;
-}
-
 // The shred side from the encoded codewords on: the slice Merkle trees (roots and every shred's
-// path), slice_sig = sign(SliceCommitment(header, root)) on the side stream while the main
-// stream serializes the 64 datagrams per slice (header and signature shared by the slice's
-// rows), then the signatures patched in.  roots_out / sigs_out null: context scratch.
+// path), slice_sig = sign(SliceCommitment(header, root)) on the side stream, forked behind the
+// roots (one signature per lane: latency-bound), while the main stream serializes the 64
+// datagrams per slice (header and signature shared by the slice's rows), then the signatures
+// patched in.  The sign's table and scratch are made ready on the main stream, before the fork:
+// the validation uses the same scratch there.  roots_out / sigs_out null: context scratch.
 // d_sizes (device, nullable): one shred size per slice -- the var Merkle build, rows packed at
 // the slice's own size (S is 0 then); null: shreds of S bytes in the rows of `k`.
 // nblocks > 0: the block hashes over the roots, a chain of dependent levels a few workgroups
@@ -230,7 +206,12 @@ int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const ui
                                         ag::kPipeShreds * kPipeProofBytes)
                     : kind_merkle(c, k, n, S, codewords, cw_stride, roots, proofs)))
     return st;
-  if ((st = sign_on_side(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs))) return st;
+  if ((st = slice_sign_prepare(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs, nullptr))) return st;
+  SideScope side(c);
+  if ((st = side.open()) ||
+      (st = slice_sign_enqueue(c, n, seed, pk, slots, slice_indices, is_last, roots, sigs, nullptr, side.stream())) ||
+      (st = side.close()))
+    return st;
   ag::PipeExpandParams ep{};
   ep.nslices = n;
   ep.shred_bytes = static_cast<uint32_t>(S);
@@ -240,7 +221,7 @@ int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const ui
   ep.data_len = reinterpret_cast<uint32_t*>(dlen);
   ep.height = reinterpret_cast<uint32_t*>(height);
   ep.slice_bytes = d_sizes;
-  if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
+  AG_HIP(ag::launch_pipe_expand(ep, c->stream));
   ag::ShredColumns cols{};
   cols.kind = kind;
   cols.slot = const_cast<uint64_t*>(slots);
@@ -259,13 +240,11 @@ int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const ui
   cols.height = ep.height;
   cols.hdr_group = ag::kPipeShreds;
   cols.skip_sig = 1;
-  if (ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
-    return drain_side(c, AG_RS_ERR_DEVICE);
+  AG_HIP(ag::launch_shred_serialize(cols, N, packets, packet_stride, packet_lens, c->stream));
   if (nblocks && (st = ag_block_tree_batch(c, nblocks, block_counts, roots, block_hashes_out, nullptr, 0, nullptr, 0)))
-    return drain_side(c, st);
-  if (hipStreamWaitEvent(c->stream, c->side_join, 0) != hipSuccess) return drain_side(c, AG_RS_ERR_DEVICE);
-  if (ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream) != hipSuccess)
-    return AG_RS_ERR_DEVICE;
+    return st;
+  if ((st = side.join())) return st;
+  AG_HIP(ag::launch_shred_sig_patch(cols, N, packets, packet_stride, packet_lens, c->stream));
   return AG_RS_OK;
 }
 
@@ -325,8 +304,7 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
     return st;
   uint8_t *plaus, *dlist, *per_slice;
   if ((st = pipe_buf(c, kBufPlausible, N, &plaus)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &dlist)) ||
-      (st = pipe_buf(c, kBufPerSlice, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice)) ||
-      (st = c->ensure_side_stream()))
+      (st = pipe_buf(c, kBufPerSlice, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice)))
     return st;
   ag::ShredColumns& cols = v->cols;
   cols = ag::ShredColumns{};
@@ -386,21 +364,29 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   mp.skip_row = k.skip;
   mp.leaf_sizes = d_sizes;  // (the full pass: one size per 64 rows, the leaf address follows the packed rows)
   mp.size_group = d_sizes ? ag::kPipeShreds : 0;
-  AG_HIP(hipEventRecord(c->side_fork, c->stream));
-  if (hipStreamWaitEvent(c->side, c->side_fork, 0) != hipSuccess ||
-      ag::launch_merkle_verify(mp, c->side) != hipSuccess || hipEventRecord(c->side_join, c->side) != hipSuccess)
-    return drain_side(c, AG_RS_ERR_DEVICE);
-  if ((st = shred_validate_impl(c, n, gdata, row, row, pp.g_shred_index, gproof, kPipeProofBytes, ag::kPipeHeight,
-                                pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, nullptr, pstat,
-                                nullptr, commits, nullptr, 0, 0, 0, 0, false, d_sizes, d_sizes ? 1 : 0)))
-    return drain_side(c, st);
-  if (ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream) != hipSuccess ||
-      hipStreamWaitEvent(c->stream, c->side_join, 0) != hipSuccess)
-    return drain_side(c, AG_RS_ERR_DEVICE);
-  if ((st = shred_validate_impl(c, N, cols.data, row, row, cols.shred_index, proof, kPipeProofBytes, ag::kPipeHeight,
-                                cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds, plaus,
-                                vstat, roots, nullptr, leaf_nodes, leaf_nodes_stride, leaves_per_tree, k.group_stride,
-                                k.skip, true)))
+  SideScope side(c);
+  if ((st = side.open())) return st;
+  AG_HIP(ag::launch_merkle_verify(mp, side.stream()));
+  if ((st = side.close())) return st;
+  ag::MerkleVerifyParams gp{};  // the picked rows: one per slice, at a slice's own size when the sizes are mixed
+  gp.leaves = gdata;
+  gp.leaf_stride = row;
+  gp.leaf_bytes = static_cast<uint32_t>(row);
+  gp.height = ag::kPipeHeight;
+  gp.index = pp.g_shred_index;
+  gp.proofs = gproof;
+  gp.proofs_stride = kPipeProofBytes;
+  gp.n = n;
+  gp.leaf_sizes = d_sizes;
+  gp.size_group = d_sizes ? 1 : 0;
+  if ((st = shred_validate_impl(c, gp, pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, pstat,
+                                nullptr, commits, false)))
+    return st;
+  AG_HIP(ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream));
+  if ((st = side.join())) return st;
+  // the side stream derived every plausible shred's root from `mp`: roots_ready
+  if ((st = shred_validate_impl(c, mp, cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds,
+                                vstat, roots, nullptr, /*roots_ready=*/true)))
     return st;
   // 32-byte rows first: the Merkle build wants 16-byte aligned roots
   v->sroot = per_slice;
@@ -1050,8 +1036,8 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     // AONT: the SHA-256 of every decoded ciphertext (decrypt_payload's key mask) runs on the side
     // stream, overlapping the Merkle rebuild, the root comparison and the absent datagrams'
     // serialization below (all of them only read the rows); one SHA-256 chain per slice leaves
-    // most of the chip's issue slots to them
-    bool sha_side = false;
+    // most of the chip's issue slots to them.  Forked here, joined in step 5's decrypt.
+    SideScope sha(c);
     if (k.aon == AG_AON_AONT) {
       std::vector<uint32_t> shl(n);
       uint32_t mx = ag::kCipherKeyBytes;
@@ -1070,12 +1056,9 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
       sb.lens = c->d_aon_lens2.as<uint32_t>();
       sb.n = n;
       sb.max_len = mx;
-      AG_HIP(hipEventRecord(c->side_fork, c->stream));
-      AG_HIP(hipStreamWaitEvent(c->side, c->side_fork, 0));
-      if (ag::launch_sha256(sb, ag::kCipherKeyBytes, c->d_aon_digests.as<uint8_t>(), c->side) != hipSuccess)
-        return AG_RS_ERR_DEVICE;
-      AG_HIP(hipEventRecord(c->side_join, c->side));
-      sha_side = true;
+      if ((st = sha.open())) return st;
+      AG_HIP(ag::launch_sha256(sb, ag::kCipherKeyBytes, c->d_aon_digests.as<uint8_t>(), sha.stream()));
+      if ((st = sha.close())) return st;
     }
     // 5. check_merkle_tree over the raw output shreds (before any decryption: they are the
     //    codeword rows)
@@ -1101,7 +1084,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
       std::vector<uint32_t> cl(n);
       for (size_t s = 0; s < n; ++s) cl[s] = pre_ok[s] ? static_cast<uint32_t>(plen[s]) : 0;
       std::vector<int64_t> pl(n);
-      if (sha_side) {
+      if (sha.is_open()) {
         // decrypt_payload with the side stream's digests (ag_aon_decrypt_batch's key and
         // length rules; the digests of the slices decrypted here hash the same lengths)
         for (size_t s = 0; s < n; ++s) {
@@ -1114,7 +1097,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
         if ((st = aon_batch(c, n, codewords, cw_stride, cl.data(), 0, &bb)) ||
             (st = c->d_aon_keys.ensure(n * 16, c->stream)))
           return st;
-        AG_HIP(hipStreamWaitEvent(c->stream, c->side_join, 0));
+        if ((st = sha.join())) return st;
         if (ag::launch_derive_keys(bb, 1, c->d_aon_digests.as<uint8_t>(), c->d_aon_keys.as<uint8_t>(), c->stream) !=
                 hipSuccess ||
             ag::launch_apply_keystream(bb, c->d_aon_keys.as<uint8_t>(), ag::kCipherKeyBytes, c->stream) != hipSuccess)
@@ -1134,9 +1117,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
                   slice_indices_out, is_last_out);
     return AG_RS_OK;
   };
-  // the side-stream rule for AONT's SHA-256, which a pass forks in step 4 and joins in step
-  // 5's decrypt: an error anywhere in a pass drains the side stream
-  if ((st = run_pass(fast_ok ? 0 : 1))) return drain_side(c, st);
+  if ((st = run_pass(fast_ok ? 0 : 1))) return st;
   if (!rerun.empty()) {
     // 6b. the batched EXACT pass over the listed slices; their entries replace pass 0's
     RerunResult rr;
@@ -1149,7 +1130,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
       // PETS / AONT would still have to serialize its absent datagrams from the encrypted rows
       // and decrypt it, stages that run over the whole batch inside a pass and have run already.
       // Correct before cheap: the batch is redone with EXACT, which does exactly that.
-      if ((st = run_pass(1))) return drain_side(c, st);
+      if ((st = run_pass(1))) return st;
     } else {
       for (size_t r = 0; r < rerun.size(); ++r) {
         const size_t s = rerun[r];

@@ -7,6 +7,11 @@ on the same context and with nothing synchronised in between, with other content
 both results are then compared with the oracles the neighbouring tests use (rs_oracle's
 ReedSolomonCoder, merkle_oracle's trees).  The two synchronous deshreds run once each, with
 per-slice patterns, directly behind a shred.
+
+The composed shred signs on the context's side stream with scratch it shares with the shred
+validation of the main stream (SideScope in csrc/rs_ctx.hpp): on a fresh context, whose buffers
+start empty, it runs as the first call and again at once with more slices, and directly behind an
+asynchronous validation whose scratch it has to regrow, against shredder_oracle's datagrams.
 """
 
 import random
@@ -16,6 +21,8 @@ import pytest
 
 import merkle_oracle as mk
 import rs_oracle as o
+import shredder_cases as cases
+import shredder_oracle as so
 from alpenglow_amd import rs
 
 N1, N2 = 2, 70           # the second batch is larger: its staging has to grow
@@ -233,3 +240,109 @@ def test_coder_deshred_batch_var_behind_a_shred(ctx, dev, mixed):
     small.check_codewords(cw)
     assert list(res) == [d[0] for d in big.deshred] == big.lens
     big.check_codewords(damaged, [d[1] for d in big.deshred])
+
+
+# ---- the composed shred's side-stream sign on a fresh context ------------------------------------
+
+@pytest.fixture(scope="module")
+def shredded():
+    """N1 + N2 Regular slices of S_UNI-byte shreds (seeded, as shredder_cases makes them) and the
+    oracle's shred of each: (datagrams, RawShreds, root, signature).  Computed once, read-only."""
+    slices = cases.random_slices(random.Random(41), so.REGULAR, S_UNI, N1 + N2)
+    return slices, [so.shred(*s[:5], cases.SEED) for s in slices]
+
+
+def fresh_context(ctx):
+    """A context whose buffers start empty, on the stream the `dev` fixture set on ctx."""
+    c = rs.Context()
+    c.set_stream(ctx.stream)
+    return c
+
+
+class ShredCall:
+    """One rs.shredder_shred_batch: its inputs and FILL-ed outputs on the device (made before any
+    call of a test starts, since an upload from pageable memory waits for the stream), the call
+    itself without anything synchronised, and the comparison with the oracle."""
+
+    def __init__(self, dev, slices):
+        self.slices = slices
+        n = len(slices)
+        self.maxd = max(len(s[1]) for s in slices)
+        data = np.zeros((n, self.maxd), np.uint8)
+        for b, s in enumerate(slices):
+            data[b, :len(s[1])] = np.frombuffer(s[1], np.uint8)
+        self.data = to_dev(data, dev)
+        self.slots, self.sidx = (to_dev(np.array([s[i] for s in slices], np.uint64), dev) for i in (2, 3))
+        self.last = to_dev(np.array([s[4] for s in slices], np.uint8), dev)
+        self.seed, self.pk = (to_dev(np.frombuffer(x, np.uint8), dev) for x in (cases.SEED, cases.PK))
+        self.cw = torch.full((n, 64 * S_UNI), FILL, dtype=torch.uint8, device=dev)
+        self.pkts = torch.full((n * 64, cases.PKT), FILL, dtype=torch.uint8, device=dev)
+        self.lens = torch.zeros(n * 64, dtype=torch.int32, device=dev)
+        self.roots = torch.full((n, 32), FILL, dtype=torch.uint8, device=dev)
+        self.sigs = torch.full((n, 64), FILL, dtype=torch.uint8, device=dev)
+
+    def run(self, c):
+        s = self.slices
+        rs.shredder_shred_batch(c, len(s), S_UNI, [x[0] for x in s], self.data, self.maxd, [len(x[1]) for x in s],
+                                self.slots, self.sidx, self.last, self.seed, self.pk, self.cw, self.pkts, cases.PKT,
+                                self.lens, roots_out=self.roots, sigs_out=self.sigs)
+
+    def check(self, want):
+        """Packets, packet lengths, roots and signatures against the oracle's; FILL past each datagram."""
+        pkts, lens, roots, sigs = (t.cpu().numpy() for t in (self.pkts, self.lens, self.roots, self.sigs))
+        for b, (datagrams, _, root, sig) in enumerate(want):
+            assert roots[b].tobytes() == root, (len(want), b)
+            assert sigs[b].tobytes() == sig, (len(want), b)
+            for j in range(64):
+                t = 64 * b + j
+                assert lens[t] == len(datagrams[j]) == cases.wire_len(S_UNI), (len(want), b, j)
+                assert pkts[t, :lens[t]].tobytes() == datagrams[j], (len(want), b, j)
+                assert (pkts[t, lens[t]:] == FILL).all(), (len(want), b, j)
+
+
+@pytest.mark.gpu
+def test_shredder_shred_batch_first_call_then_regrown(ctx, dev, shredded):
+    """The first call creates the side stream and initialises the Ed25519 table inside a composed
+    call; the second grows the sign scratch (49 * 70 > 49 * 2 bytes of commitments, 4 * 71 > 4 * 3
+    of list) while the first call's side-stream work may still run."""
+    slices, want = shredded
+    calls = [ShredCall(dev, slices[:N1]), ShredCall(dev, slices[N1:])]
+    c = fresh_context(ctx)
+    try:
+        c.synchronize()
+        for call in calls:  # back to back
+            call.run(c)
+        c.synchronize()
+        calls[0].check(want[:N1])
+        calls[1].check(want[N1:])
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+def test_shredder_shred_batch_behind_a_validation(ctx, dev, shredded):
+    """The validation of one slice's 64 shreds leaves 49 * 64 bytes of commitments and 4 * 65 of
+    list in use on the main stream; the sign of 70 slices needs 49 * 70 and 4 * 71, so both grow
+    under the queued validation."""
+    slices, want = shredded
+    (_, _, slot, slice_index, is_last, _), (_, raw, _, sig) = slices[0], want[0]
+    rows = list(raw.data) + list(raw.coding)
+    tree = mk.slice_tree(raw.data, raw.coding)
+    proofs = b"".join(b"".join(tree.create_proof(j)) for j in range(64))
+    d_rows, d_proofs, d_sigs = (to_dev(np.frombuffer(x, np.uint8), dev) for x in (b"".join(rows), proofs, sig * 64))
+    d_index = to_dev(np.arange(64, dtype=np.uint32), dev)
+    d_slot, d_sidx = (to_dev(np.full(64, x, np.uint64), dev) for x in (slot, slice_index))
+    d_last = to_dev(np.full(64, is_last, np.uint8), dev)
+    status = torch.full((64,), 9, dtype=torch.uint8, device=dev)
+    call = ShredCall(dev, slices[N1:])
+    c = fresh_context(ctx)
+    try:
+        c.synchronize()
+        rs.shred_validate_batch(c, 64, d_rows, S_UNI, S_UNI, d_index, d_proofs, 32 * so.HEIGHT, so.HEIGHT, d_slot,
+                                d_sidx, d_last, d_sigs, 64, call.pk, status)
+        call.run(c)  # at once: the validation is still queued
+        c.synchronize()
+        assert status.cpu().numpy().tolist() == [rs.SHRED_OK] * 64
+        call.check(want[N1:])
+    finally:
+        c.close()
