@@ -22,23 +22,11 @@ constexpr size_t kMinCodewordStride = 32768;  // a framed payload is at most 32 
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-// Consecutive 256-byte aligned pieces of one buffer (base null: sizes only).
-struct Carve {
-  uint8_t* base;
-  size_t at = 0;
-  template <typename T>
-  T* take(size_t count) {
-    T* out = base ? reinterpret_cast<T*>(base + at) : nullptr;
-    at += (count * sizeof(T) + 255) / 256 * 256;
-    return out;
-  }
-};
-
 // The scratch, then the staged host outputs (contiguous: one copy).  Returns the total; *out_at /
 // *out_bytes: where the staged outputs lie.
 size_t carve(uint8_t* base, size_t nblocks, size_t nrows, bool want_hashes, ag::BlockParams* p, size_t* out_at,
              size_t* out_bytes) {
-  Carve c{base};
+  Carver c{base};
   p->roots = c.take<uint8_t>(32 * nrows);
   p->first = c.take<uint64_t>(nblocks);
   p->count = c.take<uint32_t>(nblocks);
@@ -50,7 +38,7 @@ size_t carve(uint8_t* base, size_t nblocks, size_t nrows, bool want_hashes, ag::
   p->row_bad = c.take<uint8_t>(nrows);
   p->row_first = c.take<uint32_t>(nrows);
   p->fit = c.take<uint32_t>(1);
-  *out_at = c.at;
+  *out_at = c.used;
   p->tx_first = c.take<uint64_t>(nblocks);
   p->tx_bytes = c.take<uint64_t>(nblocks);
   p->tx_total = c.take<uint64_t>(1);
@@ -60,8 +48,8 @@ size_t carve(uint8_t* base, size_t nblocks, size_t nrows, bool want_hashes, ag::
   if (!want_hashes) p->hashes = nullptr;
   p->parents = c.take<uint8_t>(ag::kBlockParentBytes * nblocks);
   p->verdict = c.take<uint8_t>(nblocks);
-  *out_bytes = c.at - *out_at;
-  return c.at;
+  *out_bytes = c.used - *out_at;
+  return c.used;
 }
 
 }  // namespace

@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <numeric>
 #include <vector>
 
@@ -26,14 +25,10 @@ int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_i
                              uint8_t* packets, size_t packet_stride, uint32_t* packet_lens, uint8_t* commitments,
                              uint32_t* shred_bytes, int32_t* last_slice, uint8_t* verdict, uint32_t* shred_bytes_out,
                              uint32_t* counts_out) {
-  size_t need = 0;
   if (!c || nslots == 0 || nslots >= kIntakeMax || slices_per_slot == 0 ||
       slices_per_slot > ag::kMaxSlicesPerBlock || nslots * slices_per_slot >= kIntakeMax || n >= kIntakeMax ||
       !slot_ids || !packets || !packet_lens || !commitments || !shred_bytes || !last_slice ||
-      (n && (!rx || !rx_lens || !pk || !verdict)) ||
-      ag_shred_datagram_bytes(AG_RS_MAX_DATA_PER_SHRED, ag::kPipeHeight, &need) || packet_stride < need ||
-      packet_stride % 16 || reinterpret_cast<uintptr_t>(packets) % 16 ||
-      (n && (rx_stride < need || rx_stride % 16 || reinterpret_cast<uintptr_t>(rx) % 16)))
+      (n && (!rx || !rx_lens || !pk || !verdict)) || !intake_buffers_ok(packets, packet_stride, n, rx, rx_stride))
     return AG_RS_ERR_INVALID_ARGUMENT;
   const size_t nrows = nslots * slices_per_slot;
   // the window sorted by slot id (the kernels search it), each id with the caller's index
@@ -53,9 +48,7 @@ int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_i
   }
   if ((st = c->intake_win.send(12 * nslots, c->stream))) return st;
   IntakeScratch s;
-  if ((st = c->d_intake.ensure(carve(nullptr, n, nrows, nslots, &s), c->stream))) return st;
-  carve(c->d_intake.as<uint8_t>(), n, nrows, nslots, &s);
-  if ((st = c->h_intake.ensure(8 * nrows))) return st;
+  if ((st = intake_scratch(c, n, nrows, nslots, 0, &s))) return st;
   hipStream_t q = c->stream;
 
   ag::IntakeParams p{};
@@ -77,8 +70,7 @@ int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_i
   p.verdict = verdict;
   bind_scratch(s, &p);
 
-  AG_HIP(hipMemsetAsync(s.ok, 0, s.zero_bytes, q));
-  AG_HIP(hipMemsetAsync(s.pick, 0xFF, s.none_bytes, q));
+  if ((st = clear_scratch(s, q))) return st;
   if (n) {
     if ((st = ensure_ed_base(c))) return st;
     // parse + key: the datagrams' fields (payload, signature and path to aligned scratch rows),
@@ -86,32 +78,12 @@ int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_i
     AG_HIP(ag::launch_shred_deserialize(rx, rx_stride, rx_lens, n, s.cols, s.wire, q));
     AG_HIP(ag::launch_intake_key(p, q));
     // root and commitment of every plausible datagram (leaves of their own sizes)
-    ag::MerkleVerifyParams mv{};
-    mv.leaves = s.cols.data;
-    mv.leaf_stride = s.cols.data_stride;
-    mv.height = ag::kPipeHeight;
-    mv.index = s.cols.shred_index;
-    mv.proofs = s.cols.proof;
-    mv.proofs_stride = kProofBytes;
-    mv.n = n;
-    mv.roots_out = s.roots;
-    mv.active = s.plausible;
-    mv.list = s.mlist;
-    mv.leaf_sizes = s.cols.data_len;
-    mv.size_group = 1;
-    AG_HIP(ag::launch_merkle_verify(mv, q));
+    AG_HIP(ag::launch_merkle_verify(root_derivation(s, n), q));
     AG_HIP(ag::launch_intake_commit(p, q));
     // cache resolution: the picks' signatures, then everything not equal to a valid cache
-    ag::EdVerifyParams ev{};
+    ag::EdVerifyParams ev = commitment_verify(s, c->d_ed_base.as<int32_t>());
     ev.pks = pk;
     ev.pk_stride = 0;
-    ev.msgs = s.commit;
-    ev.msg_stride = ag::kIntakeCommitStride;
-    ev.msg_len = ag::kSliceCommitmentLen;
-    ev.sigs = s.cols.sig;
-    ev.sig_stride = 64;
-    ev.ok = s.ok;
-    ev.base_table = c->d_ed_base.as<int32_t>();
     ev.n = std::min(n, nrows);
     ev.list = s.list1;
     ev.list_count = s.counts;
@@ -128,10 +100,5 @@ int ag_shredder_intake_batch(ag_rs_ctx* c, size_t nslots, const uint64_t* slot_i
     AG_HIP(ag::launch_intake_route(p, q));
   }
   AG_HIP(ag::launch_intake_finalize(p, q));
-  uint32_t* h = c->h_intake.as<uint32_t>();
-  AG_HIP(hipMemcpyAsync(h, s.out, 8 * nrows, hipMemcpyDeviceToHost, q));
-  AG_HIP(hipStreamSynchronize(q));
-  if (shred_bytes_out) std::memcpy(shred_bytes_out, h, 4 * nrows);
-  if (counts_out) std::memcpy(counts_out, h + nrows, 4 * nrows);
-  return AG_RS_OK;
+  return read_back(c, s, nrows, shred_bytes_out, counts_out);
 }

@@ -62,6 +62,20 @@ struct DevBuf {
 };
 static_assert(!std::is_copy_constructible_v<DevBuf> && !std::is_copy_assignable_v<DevBuf>);
 
+// The typed sections of one buffer, each 256-byte aligned, in the order they are taken.  A call's
+// scratch layout is a struct of typed pointers and a carve function that fills it; the function
+// runs twice, over a null base for the size the buffer is grown to, then over the buffer.
+struct Carver {
+  uint8_t* base;
+  size_t used = 0;
+  template <typename T>
+  T* take(size_t count) {
+    T* out = base ? reinterpret_cast<T*>(base + used) : nullptr;
+    used += (count * sizeof(T) + 255) / 256 * 256;
+    return out;
+  }
+};
+
 // Grow-only pinned host buffer, mapped and coherent (fine-grained: never cached in the GPU's
 // L2, so one call's kernels cannot read another call's stale bytes): the crate-API
 // single-call kernels read and write it directly (zero-copy).  Owns its memory like DevBuf.
@@ -183,6 +197,7 @@ struct StagedUpload {
 }  // namespace host
 }  // namespace ag
 
+using ag::host::Carver;
 using ag::host::DevBuf;
 using ag::host::PinBuf;
 using ag::host::StagedUpload;
@@ -235,18 +250,16 @@ struct ag_rs_ctx {
   PinBuf h_strip;                           // coder deshred batches: pinned staging of the results
   PinBuf h_slice_meta;                      // slice parse batches: pinned staging of the results
   PinBuf h_pipe_meta;                       // composed deshreds: pinned staging of the per-slice columns
-  StagedUpload rerun;                       // their EXACT re-run: list | sizes | column prefix (sent into pipe scratch)
+  StagedUpload rerun;                       // their EXACT re-run: list | sizes | column prefix (sent into d_pipe_rerun)
   uint64_t last_rerun_slices = 0, last_rerun_passes = 0;  // the last composed deshred's EXACT re-run (test aid)
   DevBuf d_ed_base;                         // Ed25519 fixed-base table (ed25519.hpp)
-  static constexpr int kPipeBufs = 37;
-  DevBuf pipe[kPipeBufs];                   // composed shredder scratch (shredder_api.cpp's PipeBuf roles)
+  DevBuf d_pipe;                            // composed shredders: one call's scratch, grown at entry (shredder_api.cpp carves it up)
+  DevBuf d_pipe_rerun;                      // their EXACT re-run's scratch: grown in mid-call, so never part of d_pipe
   DevBuf d_sh_roots, d_sh_commit, d_sh_onvalid, d_sh_list;  // shred validation scratch
-  DevBuf d_intake;                          // shred intake scratch (intake_api.cpp carves it up)
-  StagedUpload intake_win;                  // its window: slot ids ascending (u64), then their indices (u32)
-  PinBuf h_intake;                          // pinned staging of its per-row host outputs
-  DevBuf d_repair;                          // repair intake scratch (repair_api.cpp: intake's layout + key rows)
-  StagedUpload repair_blocks;               // its blocks' slot ids (u64), in the caller's order
-  PinBuf h_repair;                          // pinned staging of its per-row host outputs
+  DevBuf d_intake;                          // shred / repair intake scratch (intake_scratch.hpp carves it up)
+  StagedUpload intake_win;                  // shred intake: slot ids ascending (u64), then their indices (u32);
+                                            // repair intake: its blocks' slot ids (u64), in the caller's order
+  PinBuf h_intake;                          // pinned staging of their per-row host outputs
   DevBuf d_block;                           // block assembly scratch and staged outputs (block_api.cpp carves it up)
   StagedUpload block_cols;                  // its host columns: data lengths | parent ids | row_ok | parent flags
   PinBuf h_block;                           // pinned staging of its host outputs

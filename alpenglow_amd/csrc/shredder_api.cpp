@@ -29,84 +29,160 @@ namespace {
 
 constexpr size_t kPipeProofBytes = 32 * ag::kPipeHeight;  // one Merkle path of a slice tree
 
-// The roles of the composed shredders' scratch (ag_rs_ctx::pipe): one grow-only buffer per role,
-// shared by every entry point of a context (calls on a context are ordered on its stream).  The
-// shred side uses the per-shred columns it writes and the two per-slice buffers at the end.
-// No two roles share a buffer.  One role has two users in the Regular deshred: kBufMerkleList
-// is the compaction list of the proof verify (side stream) and then of the Merkle rebuild (main
-// stream) -- safe because the main stream joins the side stream before the second validation,
-// long before the rebuild is enqueued.
-enum PipeBuf : int {
-  // per shred (N = 64 n rows): the ShredColumns of both sides
-  kBufKind,
-  kBufSlot,
-  kBufSliceIndex,
-  kBufIsLast,
-  kBufShredIndex,
-  kBufDataLen,
-  kBufSig,
-  kBufProof,
-  kBufHeight,
-  // per shred, deshred side
-  kBufWire,        // deserialize status
-  kBufValStatus,   // the full validation's status
-  kBufRoots,       // every plausible shred's derived root
-  kBufPlausible,   // the datagram parsed and fits its slot
-  kBufMerkleList,  // 4 (N + 1): list scratch of the Merkle kernels
-  kBufLeafFlags,   // Regular: leaves the rebuild hashes again
-  kBufFreshLens,   // 4 N: lengths of the datagrams fill_missing serialized
-  // per slice, deshred side: the picked shred (pipe_pick) and its validation
-  kBufPick,
-  kBufPickData,
-  kBufPickProof,
-  kBufPickSlot,
-  kBufPickSliceIndex,
-  kBufPickIsLast,
-  kBufPickShredIndex,
-  kBufPickSig,
-  kBufPickStatus,
-  kBufCommits,
-  kBufHasCached,
-  kBufPerSlice,     // pipe_check's outputs and the rebuilt roots (carved up by deshred_front)
-  kBufCoderWords,   // CodingOnly / PETS: the kept shreds as codeword-row present words
-  kBufSame,         // rebuilt root == signed root
-  kBufSliceOk,      // the slices fill_missing serves
-  // per slice, shred side (callers that pass no roots_out / sigs_out)
-  kBufSliceRoots,
-  kBufSliceSigs,
-  // the batched EXACT re-run of a deshred (rerun_exact), per listed slice
-  kBufRerunList,       // list | sizes | column prefix (uint32)
-  kBufRerunCodewords,  // the compact codewords
-  kBufRerunMeta,       // signed roots | rebuilt roots | kept-shred words | root comparison
-  kBufRerunProofs,     // the rebuilt trees' 64 paths
-  kPipeBufCount
-};
-static_assert(kPipeBufCount == ag_rs_ctx::kPipeBufs);
+// The composed shredders' scratch: two buffers of the context, each carved into a typed layout
+// (Carver, rs_ctx.hpp).  d_pipe holds one call's scratch -- every size follows from the slice
+// count, the row capacity and the kind, so an entry point grows it once, before its first launch,
+// and carves ShredScratch or DeshredScratch out of it; calls on a context are ordered on its
+// stream, so the two layouts share the bytes.  d_pipe_rerun holds the EXACT re-run's (RerunScratch):
+// sized by the listed slices and so grown in mid-call, which must not move d_pipe under the
+// kernels already queued.
 
-int pipe_buf(ag_rs_ctx* c, PipeBuf i, size_t bytes, uint8_t** out) {
-  const int st = c->pipe[i].ensure(std::max<size_t>(bytes, 64), c->stream);
+// The shred side: the per-shred columns shred_tail writes (N = 64 n rows), and the per-slice roots
+// and signatures of callers that pass no roots_out / sigs_out.
+struct ShredScratch {
+  uint8_t *kind, *proof, *roots, *sigs;
+  uint32_t *shred_index, *data_len, *height;
+};
+size_t carve(uint8_t* base, size_t n, ShredScratch* s) {
+  const size_t N = n * ag::kPipeShreds;
+  Carver c{base};
+  s->roots = c.take<uint8_t>(32 * n);
+  s->sigs = c.take<uint8_t>(64 * n);
+  s->kind = c.take<uint8_t>(N);
+  s->shred_index = c.take<uint32_t>(N);
+  s->data_len = c.take<uint32_t>(N);
+  s->height = c.take<uint32_t>(N);
+  s->proof = c.take<uint8_t>(kPipeProofBytes * N);
+  return c.used;
+}
+int shred_scratch(ag_rs_ctx* c, size_t n, ShredScratch* s) {
+  const int st = c->d_pipe.ensure(carve(nullptr, n, s), c->stream);
   if (st) return st;
-  *out = c->pipe[i].as<uint8_t>();
+  carve(c->d_pipe.as<uint8_t>(), n, s);
   return AG_RS_OK;
 }
 
-// The per-slice columns pipe_check writes (present | slot | slice index | is_last, contiguous
-// from `present`) read back in one copy into pinned staging: views valid until the next call
-// on the context
+// The per-slice columns pipe_check writes, as read_pipe_meta brings them to the host in one copy
+// (pinned staging: valid until the next call on the context)
 struct PipeMeta {
   const uint64_t *present, *slot, *sidx;
   const uint8_t* last;
 };
-int read_pipe_meta(ag_rs_ctx* c, const uint64_t* d_present, size_t n, PipeMeta* m) {
+
+// The deshred side: what steps 1-3 (deshred_front) leave for the later ones, and the later
+// steps' own columns.
+struct DeshredScratch {
+  // per shred (N = 64 n rows): the parsed columns (payload rows go straight into their codeword
+  // rows: deshred_front sets cols.data and the row addressing)
+  ag::ShredColumns cols{};
+  uint8_t* wire;          // deserialize status
+  uint8_t* val_status;    // the full validation's status
+  uint8_t* roots;         // [N][32] every plausible shred's derived root
+  uint8_t* plausible;     // the datagram parsed and fits its slot
+  // [N + 1] list scratch of the Merkle kernels.  Two users in the Regular deshred: the compaction
+  // list of the proof verify (side stream) and then of the Merkle rebuild (main stream) -- safe
+  // because the main stream joins the side stream before the second validation, long before the
+  // rebuild is enqueued.
+  uint32_t* merkle_list;
+  uint8_t* leaf_flags;    // Regular: leaves the rebuild hashes again
+  uint32_t* fresh_lens;   // lengths of the datagrams fill_missing serialized
+  // per slice: the picked shred (pipe_pick) and its validation
+  uint8_t *pick, *g_data, *g_proof, *g_is_last, *g_sig, *pick_status, *commits, *has_cached;
+  uint64_t *g_slot, *g_slice_index;
+  uint32_t* g_shred_index;
+  // per slice: pipe_check's outputs and the rebuilt roots
+  uint8_t* sroot;         // [n][32] the kept shreds' signed root
+  uint8_t* roots2;        // [n][32] for the rebuilt tree's root
+  uint8_t* ssig;          // [n][64]
+  // present | slot | slice index | is_last: ONE section split by hand, 25 n contiguous bytes from
+  // d_present (read_pipe_meta's single copy)
+  uint64_t *d_present, *d_slot, *d_slice_index;
+  uint8_t* d_is_last;
+  uint64_t* coder_words;  // CodingOnly / PETS: the kept shreds as codeword-row present words (two per slice)
+  uint8_t* same;          // rebuilt root == signed root
+  uint8_t* slice_ok;      // the slices fill_missing serves
+  PipeMeta h;             // present | slot | slice index | is_last on the host
+};
+// row: the capacity of a picked row (S, or 1024 with mixed sizes); coder_words: per slice
+size_t carve(uint8_t* base, size_t n, size_t row, size_t coder_words, DeshredScratch* s) {
+  const size_t N = n * ag::kPipeShreds;
+  Carver c{base};
+  s->cols.kind = c.take<uint8_t>(N);
+  s->cols.slot = c.take<uint64_t>(N);
+  s->cols.slice_index = c.take<uint64_t>(N);
+  s->cols.is_last = c.take<uint8_t>(N);
+  s->cols.shred_index = c.take<uint32_t>(N);
+  s->cols.data_len = c.take<uint32_t>(N);
+  s->cols.sig = c.take<uint8_t>(64 * N);
+  s->cols.proof = c.take<uint8_t>(kPipeProofBytes * N);
+  s->cols.proof_stride = kPipeProofBytes;
+  s->cols.height = c.take<uint32_t>(N);
+  s->wire = c.take<uint8_t>(N);
+  s->val_status = c.take<uint8_t>(N);
+  s->roots = c.take<uint8_t>(32 * N);
+  s->plausible = c.take<uint8_t>(N);
+  s->merkle_list = c.take<uint32_t>(N + 1);
+  s->leaf_flags = c.take<uint8_t>(N);
+  s->fresh_lens = c.take<uint32_t>(N);
+  s->pick = c.take<uint8_t>(n);
+  s->g_data = c.take<uint8_t>(n * row);
+  s->g_proof = c.take<uint8_t>(kPipeProofBytes * n);
+  s->g_slot = c.take<uint64_t>(n);
+  s->g_slice_index = c.take<uint64_t>(n);
+  s->g_is_last = c.take<uint8_t>(n);
+  s->g_shred_index = c.take<uint32_t>(n);
+  s->g_sig = c.take<uint8_t>(64 * n);
+  s->pick_status = c.take<uint8_t>(n);
+  s->commits = c.take<uint8_t>(ag::kSliceCommitmentLen * n);
+  s->has_cached = c.take<uint8_t>(n);
+  s->sroot = c.take<uint8_t>(32 * n);
+  s->roots2 = c.take<uint8_t>(32 * n);
+  s->ssig = c.take<uint8_t>(64 * n);
+  if (uint8_t* meta = c.take<uint8_t>(25 * n)) {
+    s->d_present = reinterpret_cast<uint64_t*>(meta);
+    s->d_slot = s->d_present + n;
+    s->d_slice_index = s->d_slot + n;
+    s->d_is_last = meta + 24 * n;
+  }
+  s->coder_words = c.take<uint64_t>(coder_words * n);
+  s->same = c.take<uint8_t>(n);
+  s->slice_ok = c.take<uint8_t>(n);
+  return c.used;
+}
+
+// The EXACT re-run, per listed slice (R of them, compact codewords of cstride bytes).
+struct RerunScratch {
+  uint32_t *list, *sizes, *col_base;  // ONE section, list | sizes | column prefix: one upload
+  uint8_t* codewords;                 // the compact codewords
+  uint8_t *sroot, *roots;             // [R][32] signed roots, rebuilt roots
+  uint64_t* present;                  // kept-shred words
+  uint8_t* same;                      // the root comparison
+  uint8_t* proofs;                    // the rebuilt trees' 64 paths
+};
+size_t carve(uint8_t* base, size_t R, size_t cstride, RerunScratch* s) {
+  Carver c{base};
+  if ((s->list = c.take<uint32_t>(3 * R + 1))) {
+    s->sizes = s->list + R;
+    s->col_base = s->list + 2 * R;
+  }
+  s->codewords = c.take<uint8_t>(R * cstride);
+  s->sroot = c.take<uint8_t>(32 * R);
+  s->roots = c.take<uint8_t>(32 * R);
+  s->present = c.take<uint64_t>(R);
+  s->same = c.take<uint8_t>(R);
+  s->proofs = c.take<uint8_t>(R * ag::kPipeShreds * kPipeProofBytes);
+  return c.used;
+}
+
+int read_pipe_meta(ag_rs_ctx* c, size_t n, DeshredScratch* v) {
   const int st = c->h_pipe_meta.ensure(25 * n);
   if (st) return st;
-  uint8_t* h = c->h_pipe_meta.as<uint8_t>();
-  AG_HIP(hipMemcpyAsync(h, d_present, 25 * n, hipMemcpyDeviceToHost, c->stream));
+  AG_HIP(hipMemcpyAsync(c->h_pipe_meta.ptr, v->d_present, 25 * n, hipMemcpyDeviceToHost, c->stream));
   AG_HIP(hipStreamSynchronize(c->stream));
-  m->present = reinterpret_cast<const uint64_t*>(h);
-  m->slot = m->present + n;
-  m->sidx = m->slot + n;
-  m->last = h + 24 * n;
+  v->h.present = c->h_pipe_meta.as<uint64_t>();
+  v->h.slot = v->h.present + n;
+  v->h.sidx = v->h.slot + n;
+  v->h.last = c->h_pipe_meta.as<uint8_t>() + 24 * n;
   return AG_RS_OK;
 }
 
@@ -140,6 +216,14 @@ bool shredder_kind(int kind, size_t cw_stride, ShredderKind* k) {
     case AG_SHREDDER_AONT: *k = {32, 32, AG_AON_AONT, 0, 0, cw_stride}; return true;
     default: return false;
   }
+}
+// One deshred's scratch, grown and carved at entry.  row: S, or 1024 with mixed sizes.
+int deshred_scratch(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t row, DeshredScratch* v) {
+  const size_t coder_words = k.m > kDataShreds ? 2 : 0;  // CodingOnly / PETS
+  const int st = c->d_pipe.ensure(carve(nullptr, n, row, coder_words, v), c->stream);
+  if (st) return st;
+  carve(c->d_pipe.as<uint8_t>(), n, row, coder_words, v);
+  return AG_RS_OK;
 }
 uint32_t kind_row(const ShredderKind& k, uint32_t j) { return k.row0 + j + (k.skip && j >= k.skip ? 1u : 0u); }
 // the kept output shreds of one slice (present bit j) as ag_rs_coder_deshred_batch's flags of its
@@ -182,25 +266,19 @@ int kind_merkle(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const u
 // roots (one signature per lane: latency-bound), while the main stream serializes the 64
 // datagrams per slice (header and signature shared by the slice's rows), then the signatures
 // patched in.  The sign's table and scratch are made ready on the main stream, before the fork:
-// the validation uses the same scratch there.  roots_out / sigs_out null: context scratch.
+// the validation uses the same scratch there.  roots_out / sigs_out null: the scratch's (sc).
 // d_sizes (device, nullable): one shred size per slice -- the var Merkle build, rows packed at
 // the slice's own size (S is 0 then); null: shreds of S bytes in the rows of `k`.
 // nblocks > 0: the block hashes over the roots, a chain of dependent levels a few workgroups
 // wide, placed where the main stream would otherwise only wait for the signatures.
-int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint32_t* d_sizes, uint8_t* codewords,
-               size_t cw_stride, const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
+int shred_tail(ag_rs_ctx* c, const ShredderKind& k, const ShredScratch& sc, size_t n, size_t S,
+               const uint32_t* d_sizes, uint8_t* codewords, size_t cw_stride, const uint64_t* slots, const uint64_t* slice_indices, const uint8_t* is_last,
                const uint8_t* seed, const uint8_t* pk, uint8_t* roots_out, uint8_t* sigs_out, uint8_t* packets,
                size_t packet_stride, uint32_t* packet_lens, size_t nblocks, const uint32_t* block_counts,
                uint8_t* block_hashes_out) {
   const size_t N = n * ag::kPipeShreds;
   int st;
-  uint8_t *roots = roots_out, *sigs = sigs_out, *proofs, *kind, *sidx, *dlen, *height;
-  if (!roots && (st = pipe_buf(c, kBufSliceRoots, 32 * n, &roots))) return st;
-  if (!sigs && (st = pipe_buf(c, kBufSliceSigs, 64 * n, &sigs))) return st;
-  if ((st = pipe_buf(c, kBufProof, kPipeProofBytes * N, &proofs)) || (st = pipe_buf(c, kBufKind, N, &kind)) ||
-      (st = pipe_buf(c, kBufShredIndex, 4 * N, &sidx)) || (st = pipe_buf(c, kBufDataLen, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, kBufHeight, 4 * N, &height)))
-    return st;
+  uint8_t *roots = roots_out ? roots_out : sc.roots, *sigs = sigs_out ? sigs_out : sc.sigs, *proofs = sc.proof;
   if (reinterpret_cast<uintptr_t>(roots) % 16) return AG_RS_ERR_INVALID_ARGUMENT;  // (the Merkle build's stores)
   if ((st = d_sizes ? merkle_var_launch(c, n, d_sizes, codewords, cw_stride, roots, nullptr, 0, proofs,
                                         ag::kPipeShreds * kPipeProofBytes)
@@ -216,14 +294,14 @@ int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const ui
   ep.nslices = n;
   ep.shred_bytes = static_cast<uint32_t>(S);
   ep.num_data = k.num_data;
-  ep.kind = kind;
-  ep.shred_index = reinterpret_cast<uint32_t*>(sidx);
-  ep.data_len = reinterpret_cast<uint32_t*>(dlen);
-  ep.height = reinterpret_cast<uint32_t*>(height);
+  ep.kind = sc.kind;
+  ep.shred_index = sc.shred_index;
+  ep.data_len = sc.data_len;
+  ep.height = sc.height;
   ep.slice_bytes = d_sizes;
   AG_HIP(ag::launch_pipe_expand(ep, c->stream));
   ag::ShredColumns cols{};
-  cols.kind = kind;
+  cols.kind = sc.kind;
   cols.slot = const_cast<uint64_t*>(slots);
   cols.slice_index = const_cast<uint64_t*>(slice_indices);
   cols.is_last = const_cast<uint8_t*>(is_last);
@@ -248,21 +326,6 @@ int shred_tail(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const ui
   return AG_RS_OK;
 }
 
-// What steps 1-3 of a deshred leave for the later ones: the per-shred columns (payload rows
-// parsed straight into their codeword rows) and, per slice, pipe_check's outputs on the device
-// and (PipeMeta) on the host.
-struct DeshredViews {
-  ag::ShredColumns cols;
-  uint8_t* wire;        // [N] deserialize status
-  uint8_t* sroot;       // [n][32] the kept shreds' signed root
-  uint8_t* roots2;      // [n][32] for the rebuilt tree's root
-  uint8_t* ssig;        // [n][64]
-  uint64_t* d_present;  // [n] the shreds kept
-  uint64_t* d_slot;
-  uint8_t *ssidx, *slast;
-  PipeMeta h;           // present | slot | slice index | is_last on the host
-};
-
 // Steps 1-3 of a deshred in the row layout `k`:
 // 1. network::deserialize (absent slots have length 0: malformed, never written);
 // 2. ValidatedShred::try_new: one signature per slice (its first plausible shred), then every
@@ -278,72 +341,41 @@ struct DeshredViews {
 // own size from k.group_stride (the slice stride; S is 0 then) -- every stage reads the slice's
 // size where it reads S: the parse (row capacity), the slot check of pick / check, the leaf size
 // of both verifies.  The picked rows are gathered at a fixed stride of 1024 bytes.
+// v: the call's carved scratch (deshred_scratch, same row capacity); the codeword addressing of
+// its columns and the host copy of pipe_check's outputs are filled in here.
 int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const uint32_t* d_sizes,
                   const uint8_t* packets, size_t packet_stride, const uint32_t* packet_lens, const uint8_t* pk,
                   uint8_t* codewords, uint8_t* leaf_nodes, size_t leaf_nodes_stride, uint32_t leaves_per_tree,
-                  DeshredViews* v) {
+                  DeshredScratch* v) {
   const size_t N = n * ag::kPipeShreds;
   const size_t row = d_sizes ? size_t{AG_RS_MAX_DATA_PER_SHRED} : S;  // row capacity; stride of the picked rows
   int st;
-  uint8_t *kind, *slot, *sidx, *last, *shidx, *dlen, *sig, *proof, *height, *wire, *vstat, *roots;
-  if ((st = pipe_buf(c, kBufKind, N, &kind)) || (st = pipe_buf(c, kBufSlot, 8 * N, &slot)) ||
-      (st = pipe_buf(c, kBufSliceIndex, 8 * N, &sidx)) || (st = pipe_buf(c, kBufIsLast, N, &last)) ||
-      (st = pipe_buf(c, kBufShredIndex, 4 * N, &shidx)) || (st = pipe_buf(c, kBufDataLen, 4 * N, &dlen)) ||
-      (st = pipe_buf(c, kBufSig, 64 * N, &sig)) || (st = pipe_buf(c, kBufProof, kPipeProofBytes * N, &proof)) ||
-      (st = pipe_buf(c, kBufHeight, 4 * N, &height)) || (st = pipe_buf(c, kBufWire, N, &wire)) ||
-      (st = pipe_buf(c, kBufValStatus, N, &vstat)) || (st = pipe_buf(c, kBufRoots, 32 * N, &roots)))
-    return st;
-  uint8_t *pick, *gdata, *gproof, *gslot, *gsidx, *glast, *gidx, *gsig, *pstat, *commits, *hasc;
-  if ((st = pipe_buf(c, kBufPick, n, &pick)) || (st = pipe_buf(c, kBufPickData, n * row, &gdata)) ||
-      (st = pipe_buf(c, kBufPickProof, kPipeProofBytes * n, &gproof)) ||
-      (st = pipe_buf(c, kBufPickSlot, 8 * n, &gslot)) || (st = pipe_buf(c, kBufPickSliceIndex, 8 * n, &gsidx)) ||
-      (st = pipe_buf(c, kBufPickIsLast, n, &glast)) || (st = pipe_buf(c, kBufPickShredIndex, 4 * n, &gidx)) ||
-      (st = pipe_buf(c, kBufPickSig, 64 * n, &gsig)) || (st = pipe_buf(c, kBufPickStatus, n, &pstat)) ||
-      (st = pipe_buf(c, kBufCommits, ag::kSliceCommitmentLen * n, &commits)) ||
-      (st = pipe_buf(c, kBufHasCached, n, &hasc)))
-    return st;
-  uint8_t *plaus, *dlist, *per_slice;
-  if ((st = pipe_buf(c, kBufPlausible, N, &plaus)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &dlist)) ||
-      (st = pipe_buf(c, kBufPerSlice, (8 + 8 + 8 + 32 + 32 + 64 + 8) * n, &per_slice)))
-    return st;
   ag::ShredColumns& cols = v->cols;
-  cols = ag::ShredColumns{};
-  cols.kind = kind;
-  cols.slot = reinterpret_cast<uint64_t*>(slot);
-  cols.slice_index = reinterpret_cast<uint64_t*>(sidx);
-  cols.is_last = last;
-  cols.shred_index = reinterpret_cast<uint32_t*>(shidx);
   cols.data = codewords + k.row0 * S;
   cols.data_stride = row;
   cols.group_stride = k.group_stride;
   cols.skip_row = k.skip;
   cols.row_sizes = d_sizes;
-  cols.data_len = reinterpret_cast<uint32_t*>(dlen);
-  cols.sig = sig;
-  cols.proof = proof;
-  cols.proof_stride = kPipeProofBytes;
-  cols.height = reinterpret_cast<uint32_t*>(height);
-  v->wire = wire;
-  if (ag::launch_shred_deserialize(packets, packet_stride, packet_lens, N, cols, wire, c->stream) != hipSuccess)
+  if (ag::launch_shred_deserialize(packets, packet_stride, packet_lens, N, cols, v->wire, c->stream) != hipSuccess)
     return AG_RS_ERR_DEVICE;
   ag::PipePickParams pp{};
   pp.nslices = n;
   pp.shred_bytes = static_cast<uint32_t>(S);
   pp.num_data = k.num_data;
-  pp.wire_status = wire;
+  pp.wire_status = v->wire;
   pp.cols = cols;
-  pp.pick = pick;
-  pp.g_data = gdata;
-  pp.g_proof = gproof;
-  pp.g_slot = reinterpret_cast<uint64_t*>(gslot);
-  pp.g_slice_index = reinterpret_cast<uint64_t*>(gsidx);
-  pp.g_is_last = glast;
-  pp.g_shred_index = reinterpret_cast<uint32_t*>(gidx);
-  pp.g_sig = gsig;
-  pp.plausible = plaus;  // per shred: the datagram parsed and fits its slot
+  pp.pick = v->pick;
+  pp.g_data = v->g_data;
+  pp.g_proof = v->g_proof;
+  pp.g_slot = v->g_slot;
+  pp.g_slice_index = v->g_slice_index;
+  pp.g_is_last = v->g_is_last;
+  pp.g_shred_index = v->g_shred_index;
+  pp.g_sig = v->g_sig;
+  pp.plausible = v->plausible;  // per shred: the datagram parsed and fits its slot
   pp.slice_bytes = d_sizes;
-  AG_HIP(hipMemsetAsync(gdata, 0, n * row, c->stream));  // slices without a pick: defined bytes
-  AG_HIP(hipMemsetAsync(gidx, 0, 4 * n, c->stream));
+  AG_HIP(hipMemsetAsync(v->g_data, 0, n * row, c->stream));  // slices without a pick: defined bytes
+  AG_HIP(hipMemsetAsync(v->g_shred_index, 0, 4 * n, c->stream));
   if (ag::launch_pipe_pick(pp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   ag::MerkleVerifyParams mp{};
   mp.leaves = cols.data;
@@ -351,12 +383,12 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   mp.leaf_bytes = static_cast<uint32_t>(S);
   mp.height = ag::kPipeHeight;
   mp.index = cols.shred_index;
-  mp.proofs = proof;
+  mp.proofs = cols.proof;
   mp.proofs_stride = kPipeProofBytes;
   mp.n = N;
-  mp.roots_out = roots;
-  mp.active = plaus;
-  mp.list = reinterpret_cast<uint32_t*>(dlist);
+  mp.roots_out = v->roots;
+  mp.active = v->plausible;
+  mp.list = v->merkle_list;
   mp.leaf_nodes = leaf_nodes;
   mp.leaf_nodes_stride = leaf_nodes_stride;
   mp.leaves_per_tree = leaves_per_tree;
@@ -369,50 +401,43 @@ int deshred_front(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const
   AG_HIP(ag::launch_merkle_verify(mp, side.stream()));
   if ((st = side.close())) return st;
   ag::MerkleVerifyParams gp{};  // the picked rows: one per slice, at a slice's own size when the sizes are mixed
-  gp.leaves = gdata;
+  gp.leaves = v->g_data;
   gp.leaf_stride = row;
   gp.leaf_bytes = static_cast<uint32_t>(row);
   gp.height = ag::kPipeHeight;
-  gp.index = pp.g_shred_index;
-  gp.proofs = gproof;
+  gp.index = v->g_shred_index;
+  gp.proofs = v->g_proof;
   gp.proofs_stride = kPipeProofBytes;
   gp.n = n;
   gp.leaf_sizes = d_sizes;
   gp.size_group = d_sizes ? 1 : 0;
-  if ((st = shred_validate_impl(c, gp, pp.g_slot, pp.g_slice_index, glast, gsig, 64, pk, nullptr, nullptr, 1, pstat,
-                                nullptr, commits, false)))
+  if ((st = shred_validate_impl(c, gp, v->g_slot, v->g_slice_index, v->g_is_last, v->g_sig, 64, pk, nullptr, nullptr, 1,
+                                v->pick_status, nullptr, v->commits, false)))
     return st;
-  AG_HIP(ag::launch_pipe_cache_flags(pick, pstat, n, hasc, c->stream));
+  AG_HIP(ag::launch_pipe_cache_flags(v->pick, v->pick_status, n, v->has_cached, c->stream));
   if ((st = side.join())) return st;
   // the side stream derived every plausible shred's root from `mp`: roots_ready
-  if ((st = shred_validate_impl(c, mp, cols.slot, cols.slice_index, last, sig, 64, pk, commits, hasc, ag::kPipeShreds,
-                                vstat, roots, nullptr, /*roots_ready=*/true)))
+  if ((st = shred_validate_impl(c, mp, cols.slot, cols.slice_index, cols.is_last, cols.sig, 64, pk, v->commits,
+                                v->has_cached, ag::kPipeShreds, v->val_status, v->roots, nullptr,
+                                /*roots_ready=*/true)))
     return st;
-  // 32-byte rows first: the Merkle build wants 16-byte aligned roots
-  v->sroot = per_slice;
-  v->roots2 = v->sroot + 32 * n;
-  v->ssig = v->roots2 + 32 * n;
-  v->d_present = reinterpret_cast<uint64_t*>(v->ssig + 64 * n);
-  v->d_slot = v->d_present + n;
-  v->ssidx = reinterpret_cast<uint8_t*>(v->d_slot + n);
-  v->slast = v->ssidx + 8 * n;
   ag::PipeCheckParams kp{};
   kp.nslices = n;
   kp.shred_bytes = static_cast<uint32_t>(S);
   kp.num_data = k.num_data;
-  kp.wire_status = wire;
-  kp.val_status = vstat;
-  kp.roots = roots;
+  kp.wire_status = v->wire;
+  kp.val_status = v->val_status;
+  kp.roots = v->roots;
   kp.cols = cols;
   kp.present = v->d_present;
   kp.root = v->sroot;
   kp.slot = v->d_slot;
-  kp.slice_index = reinterpret_cast<uint64_t*>(v->ssidx);
-  kp.is_last = v->slast;
+  kp.slice_index = v->d_slice_index;
+  kp.is_last = v->d_is_last;
   kp.sig = v->ssig;
   kp.slice_bytes = d_sizes;
   if (ag::launch_pipe_check(kp, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-  return read_pipe_meta(c, v->d_present, n, &v->h);
+  return read_pipe_meta(c, n, v);
 }
 
 // Shredder::deshred's result per slice from the coder's (plen: payload length or -error), the
@@ -446,24 +471,20 @@ void pipe_statuses(size_t n, const int64_t* plen, const uint8_t* h_same, const u
 }
 
 // fill_missing_shreds: the datagrams of the absent slots of the slices with ok[s], serialized
-// into their packets; their lengths go to *fresh (pipe_merge_lens moves the final slices'
-// lengths into packet_lens), the uploaded flags to *d_ok.  Enqueued only: `ok` is host memory
+// into their packets; their lengths go to v.fresh_lens (pipe_merge_lens moves the final slices'
+// lengths into packet_lens), the uploaded flags to v.slice_ok.  Enqueued only: `ok` is host memory
 // the upload reads, so the caller synchronizes before it changes.  Slices of mixed sizes
 // (v.cols.row_sizes, deshred_front's d_sizes): each datagram at its slice's own size.
-int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const DeshredViews& v, const uint8_t* ok,
-                 uint8_t* packets, size_t packet_stride, uint8_t** d_ok, uint32_t** fresh) {
+int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const DeshredScratch& v, const uint8_t* ok,
+                 uint8_t* packets, size_t packet_stride) {
   const size_t N = n * ag::kPipeShreds;
-  int st;
-  uint8_t* fl;
-  if ((st = pipe_buf(c, kBufSliceOk, n, d_ok)) || (st = pipe_buf(c, kBufFreshLens, 4 * N, &fl))) return st;
-  *fresh = reinterpret_cast<uint32_t*>(fl);
-  AG_HIP(hipMemcpyAsync(*d_ok, ok, n, hipMemcpyHostToDevice, c->stream));
+  AG_HIP(hipMemcpyAsync(v.slice_ok, ok, n, hipMemcpyHostToDevice, c->stream));
   ag::PipeExpandParams ep{};
   ep.nslices = n;
   ep.shred_bytes = static_cast<uint32_t>(S);
   ep.num_data = k.num_data;
   ep.skip = v.d_present;
-  ep.slice_ok = *d_ok;
+  ep.slice_ok = v.slice_ok;
   ep.kind = v.cols.kind;
   ep.shred_index = v.cols.shred_index;
   ep.data_len = v.cols.data_len;
@@ -472,11 +493,11 @@ int fill_missing(ag_rs_ctx* c, const ShredderKind& k, size_t n, size_t S, const 
   if (ag::launch_pipe_expand(ep, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   ag::ShredColumns fc = v.cols;
   fc.slot = v.d_slot;
-  fc.slice_index = reinterpret_cast<uint64_t*>(v.ssidx);
-  fc.is_last = v.slast;
+  fc.slice_index = v.d_slice_index;
+  fc.is_last = v.d_is_last;
   fc.sig = v.ssig;
   fc.hdr_group = ag::kPipeShreds;
-  if (ag::launch_shred_serialize(fc, N, packets, packet_stride, *fresh, c->stream) != hipSuccess)
+  if (ag::launch_shred_serialize(fc, N, packets, packet_stride, v.fresh_lens, c->stream) != hipSuccess)
     return AG_RS_ERR_DEVICE;
   return AG_RS_OK;
 }
@@ -508,7 +529,7 @@ struct RerunResult {
 // scattered then, the caller redoes its batch.  (It does not happen: kept shreds that no decode
 // of 32 of them reproduces are no codeword, and no codeword's tree has their signed root.)
 int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>& list, size_t S,
-                const uint32_t* sizes, const uint8_t* packets, size_t packet_stride, const DeshredViews& v,
+                const uint32_t* sizes, const uint8_t* packets, size_t packet_stride, const DeshredScratch& v,
                 uint8_t* codewords, size_t cw_stride, RerunResult* out, bool* passed) {
   const size_t R = list.size(), rows = kDataShreds + k.m;
   const bool regular = k.aon < 0 && k.m == kDataShreds;
@@ -529,15 +550,15 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
   }
   h[3 * R] = cols;
   const size_t cstride = (rows * max_s + 15) / 16 * 16;
-  uint8_t *d_list, *ccw, *meta, *c_proofs;
-  if ((st = pipe_buf(c, kBufRerunList, 4 * words, &d_list)) || (st = pipe_buf(c, kBufRerunCodewords, R * cstride, &ccw)) ||
-      (st = pipe_buf(c, kBufRerunMeta, (32 + 32 + 8 + 1) * R, &meta)) ||
-      (st = pipe_buf(c, kBufRerunProofs, R * ag::kPipeShreds * kPipeProofBytes, &c_proofs)))
-    return st;
-  if ((st = c->rerun.send(4 * words, c->stream, d_list))) return st;
-  const uint32_t* d_sizes = reinterpret_cast<const uint32_t*>(d_list) + R;
+  // a buffer of its own: growing it here leaves d_pipe (`v`, read by the queued kernels) in place
+  RerunScratch rs;
+  if ((st = c->d_pipe_rerun.ensure(carve(nullptr, R, cstride, &rs), c->stream))) return st;
+  carve(c->d_pipe_rerun.as<uint8_t>(), R, cstride, &rs);
+  if ((st = c->rerun.send(4 * words, c->stream, rs.list))) return st;
+  uint8_t *const ccw = rs.codewords, *const c_roots = rs.roots, *const c_proofs = rs.proofs;
+  const uint32_t* d_sizes = rs.sizes;
   ag::PipeRerunParams rp{};
-  rp.list = reinterpret_cast<const uint32_t*>(d_list);
+  rp.list = rs.list;
   rp.sizes = d_sizes;
   rp.nlist = static_cast<uint32_t>(R);
   rp.rows = static_cast<uint32_t>(rows);
@@ -551,11 +572,9 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
   rp.packet_stride = packet_stride;
   rp.present = v.d_present;
   rp.sroot = v.sroot;
-  rp.c_sroot = meta;  // 32-byte rows first: the Merkle build wants 16-byte aligned roots
-  uint8_t* c_roots = meta + 32 * R;
+  rp.c_sroot = rs.sroot;
   rp.c_roots = c_roots;
-  rp.c_present = reinterpret_cast<uint64_t*>(meta + 64 * R);
-  uint8_t* c_same = meta + 72 * R;
+  rp.c_present = rs.present;
   rp.roots = v.roots2;
   rp.c_proofs = c_proofs;
   rp.proofs = v.cols.proof;
@@ -565,7 +584,7 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
   if (regular) {
     c->last_encode_kernels = 0;
     c->last_window_kernels = 0;
-    if ((st = pipe_coder_deshred_var(c, R, ccw, cstride, rp.c_present, d_sizes, d_sizes + R, cols, true,
+    if ((st = pipe_coder_deshred_var(c, R, ccw, cstride, rp.c_present, d_sizes, rs.col_base, cols, true,
                                      out->plen.data(), true)) ||
         (st = merkle_var_launch(c, R, d_sizes, ccw, cstride, c_roots, nullptr, 0, c_proofs,
                                 ag::kPipeShreds * kPipeProofBytes)))
@@ -580,9 +599,9 @@ int rerun_exact(ag_rs_ctx* c, const ShredderKind& k, const std::vector<uint32_t>
   }
   c->last_rerun_slices = R;
   c->last_rerun_passes = 1;
-  if (ag::launch_pipe_root_cmp(c_roots, rp.c_sroot, R, c_same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  if (ag::launch_pipe_root_cmp(c_roots, rp.c_sroot, R, rs.same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   out->same.assign(R, 0);
-  AG_HIP(hipMemcpyAsync(out->same.data(), c_same, R, hipMemcpyDeviceToHost, c->stream));
+  AG_HIP(hipMemcpyAsync(out->same.data(), rs.same, R, hipMemcpyDeviceToHost, c->stream));
   out->sstat.assign(R, 0);
   out->parent_flag.assign(R, 0);
   out->parent_id.assign(R * AG_SLICE_BLOCK_ID_BYTES, 0);
@@ -609,11 +628,12 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
                     uint64_t* slots_out, uint64_t* slice_indices_out, uint8_t* is_last_out,
                     uint8_t* parent_flags_out, uint8_t* parent_ids_out, uint32_t* data_offsets_out,
                     uint32_t* data_lens_out) {
-  const size_t N = n * ag::kPipeShreds;
   int st;
   ShredderKind k;
   shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
   c->last_rerun_slices = c->last_rerun_passes = 0;
+  DeshredScratch v;
+  if ((st = deshred_scratch(c, k, n, sizes ? size_t{AG_RS_MAX_DATA_PER_SHRED} : S, &v))) return st;
   const uint32_t *d_sizes = nullptr, *d_col_base = nullptr;
   uint32_t total_columns = 0;
   if (sizes) {
@@ -626,7 +646,6 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
   const size_t nodes_stride = (32 * ag_merkle_node_count(ag::kPipeShreds) + 255) / 256 * 256;
   if ((st = c->d_merkle_nodes.ensure(n * nodes_stride, c->stream))) return st;
   uint8_t* nodes = c->d_merkle_nodes.as<uint8_t>();
-  DeshredViews v;
   if ((st = deshred_front(c, k, n, S, d_sizes, packets, packet_stride, packet_lens, pk, codewords, nodes, nodes_stride,
                           ag::kPipeShreds, &v)))
     return st;
@@ -674,14 +693,11 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
   //    flags below re-hash or ignore them.  A new step in between that writes kept rows or
   //    d_merkle_nodes must clear the matching present bits or re-hash.
   {
-    uint8_t *lflags, *llist;
-    if ((st = pipe_buf(c, kBufLeafFlags, N, &lflags)) || (st = pipe_buf(c, kBufMerkleList, 4 * (N + 1), &llist)) ||
-        (st = ensure_empty_roots(c)))
-      return st;
+    if ((st = ensure_empty_roots(c))) return st;
     // the host coder path (shreds not whole 64-byte chunks) re-encodes every coding shred; the
     // var coder never does: its decode restores the absent coding shreds of exactly-32 slices,
     // and the kernel flags the surplus slices' coding rows itself
-    if (ag::launch_pipe_leaf_flags(v.d_present, n, !device_coder, lflags, c->stream) != hipSuccess)
+    if (ag::launch_pipe_leaf_flags(v.d_present, n, !device_coder, v.leaf_flags, c->stream) != hipSuccess)
       return AG_RS_ERR_DEVICE;
     ag::MerkleBuildParams mb{};
     mb.leaves = codewords;
@@ -694,18 +710,16 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
     mb.roots = v.roots2;
     mb.proofs = v.cols.proof;
     mb.proofs_stride = ag::kPipeShreds * kPipeProofBytes;
-    mb.hash_leaf = lflags;
-    mb.list = reinterpret_cast<uint32_t*>(llist);
+    mb.hash_leaf = v.leaf_flags;
+    mb.list = v.merkle_list;  // (its second user: see DeshredScratch)
     mb.leaf_sizes = d_sizes;  // (leaf_stride / leaf_bytes unused then: rows at the slice's own size)
     c->last_merkle_kernels = 0;
     if (ag::launch_merkle_build(mb, nodes, nodes_stride, c->stream, &c->last_merkle_kernels) != hipSuccess)
       return AG_RS_ERR_DEVICE;
   }
-  uint8_t* same;
-  if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
-  if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+  if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, v.same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
   std::vector<uint8_t> h_same(n);
-  AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
+  AG_HIP(hipMemcpyAsync(h_same.data(), v.same, n, hipMemcpyDeviceToHost, c->stream));
   // 6. SlicePayload::try_from
   std::vector<uint8_t> sstat(n);
   if ((st = ag_slice_parse_batch(c, n, codewords, cw_stride, plen.data(), sstat.data(), parent_flags_out,
@@ -746,10 +760,8 @@ int regular_deshred(ag_rs_ctx* c, size_t n, size_t S, const uint32_t* sizes, uin
   pipe_statuses(n, plen.data(), h_same.data(), sstat.data(), v.h, 0, status, ok.data(), slots_out, slice_indices_out,
                 is_last_out);
   // 7. fill_missing_shreds: datagrams for the absent slots of the slices that succeeded
-  uint8_t* d_ok;
-  uint32_t* fresh;
-  if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
-  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
+  if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride))) return st;
+  if (ag::launch_pipe_merge_lens(v.fresh_lens, v.d_present, v.slice_ok, n, packet_lens, c->stream) != hipSuccess)
     return AG_RS_ERR_DEVICE;
   AG_HIP(hipStreamSynchronize(c->stream));  // host vectors read by async copies
   return AG_RS_OK;
@@ -774,14 +786,17 @@ int ag_shredder_shred_batch(ag_rs_ctx* c, size_t nslices, size_t S, const uint8_
   const size_t n = nslices, cw_stride = ag::kPipeShreds * S;
   ShredderKind k;
   shredder_kind(AG_SHREDDER_REGULAR, cw_stride, &k);
+  ShredScratch sc;
+  int st = shred_scratch(c, n, &sc);
+  if (st) return st;
   // 1. Slice::payload_bytes into the data regions, 2. ReedSolomonCoder::shred in place
   std::vector<uint32_t> lens(n);
-  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
-                                lens.data());
-  if (st) return st;
+  if ((st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
+                                 lens.data())))
+    return st;
   if ((st = ag_rs_coder_shred_batch(c, k.m, n, S, nullptr, 0, lens.data(), codewords, cw_stride))) return st;
   // 3. slice Merkle trees, 4. slice signatures, 5. the 64 datagrams per slice
-  return shred_tail(c, k, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
+  return shred_tail(c, k, sc, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
                     sigs_out, packets, packet_stride, packet_lens, 0, nullptr, nullptr);
 }
 
@@ -832,11 +847,14 @@ int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* par
   ShredderKind k;
   shredder_kind(AG_SHREDDER_REGULAR, codeword_stride, &k);
   k.group_stride = codeword_stride;  // rows packed at each slice's own size: addressed per slice
+  ShredScratch sc;
+  int st = shred_scratch(c, n, &sc);
+  if (st) return st;
   // 1. Slice::payload_bytes into the data regions (a framed payload is shorter than 32 * S_s, so
   //    it stays inside its own slice's data shreds), 2. ReedSolomonCoder::shred in place
-  int st = ag_slice_frame_batch(c, n, max_s, parent_flags, parent_ids, data, data_stride, data_lens, codewords,
-                                codeword_stride, lens.data());
-  if (st) return st;
+  if ((st = ag_slice_frame_batch(c, n, max_s, parent_flags, parent_ids, data, data_stride, data_lens, codewords,
+                                 codeword_stride, lens.data())))
+    return st;
   if ((st = ag_rs_coder_shred_batch_var(c, k.m, n, nullptr, 0, lens.data(), codewords, codeword_stride,
                                         shred_bytes_out)))
     return st;
@@ -844,7 +862,7 @@ int ag_shredder_shred_batch_var(ag_rs_ctx* c, size_t nslices, const uint8_t* par
   const uint32_t* d_sizes = c->lens.dev.as<uint32_t>() + n;
   // 3. slice Merkle trees, 4. slice signatures, 5. the 64 datagrams per slice (rows and data
   //    lengths at the slice's own size), 6. the block hashes over the roots
-  return shred_tail(c, k, n, 0, d_sizes, codewords, codeword_stride, slots, slice_indices, is_last, seed, pk,
+  return shred_tail(c, k, sc, n, 0, d_sizes, codewords, codeword_stride, slots, slice_indices, is_last, seed, pk,
                     roots_out, sigs_out, packets, packet_stride, packet_lens, nblocks, block_counts,
                     block_hashes_out);
 }
@@ -923,19 +941,22 @@ int ag_shredder_shred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_t 
     const size_t framed = 1 + (parent_flags[b] ? AG_SLICE_BLOCK_ID_BYTES : 0) + 8 + size_t{data_lens[b]};
     if (framed + extra > kMaxPayload) return AG_RS_ERR_TOO_MUCH_DATA;
   }
+  ShredScratch sc;
+  int st = shred_scratch(c, n, &sc);
+  if (st) return st;
   // 1. Slice::payload_bytes into the data regions; 2. PETS / AONT: encrypt_with_random_key with
   //    the caller's key + the key tail; 3. ReedSolomonCoder::shred in place
   std::vector<uint32_t> lens(n);
-  int st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
-                                lens.data());
-  if (st) return st;
+  if ((st = ag_slice_frame_batch(c, n, S, parent_flags, parent_ids, data, data_stride, data_lens, codewords, cw_stride,
+                                 lens.data())))
+    return st;
   if (k.aon >= 0) {
     if ((st = ag_aon_encrypt_batch(c, k.aon, n, keys, codewords, cw_stride, lens.data()))) return st;
     for (uint32_t& l : lens) l += static_cast<uint32_t>(ag::kCipherKeyBytes);
   }
   if ((st = ag_rs_coder_shred_batch(c, k.m, n, S, nullptr, 0, lens.data(), codewords, cw_stride))) return st;
   // 4. the 64 output shreds (data first) in place: Merkle tree, signature, datagrams over them
-  return shred_tail(c, k, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
+  return shred_tail(c, k, sc, n, S, nullptr, codewords, cw_stride, slots, slice_indices, is_last, seed, pk, roots_out,
                     sigs_out, packets, packet_stride, packet_lens, 0, nullptr, nullptr);
 }
 
@@ -977,12 +998,11 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   // (test aids: the device-pattern pass only adds to them, the coder's host-pattern route resets them)
   c->last_encode_kernels = c->last_window_kernels = 0;
   const size_t key_bytes = k.aon >= 0 ? ag::kCipherKeyBytes : 0;
-  DeshredViews v;
+  DeshredScratch v;  // one layout for both passes: a redo writes the same sections again
+  if ((st = deshred_scratch(c, k, n, S, &v))) return st;
   std::vector<uint8_t> ok(n), pre_ok(n), h_same(n), sstat(n);
   std::vector<int64_t> plen(n);
   std::vector<uint32_t> rerun;
-  uint8_t* d_ok = nullptr;
-  uint32_t* fresh = nullptr;
   const bool fast_ok = pipe_tail_ok(S, k.m, true) && n > 1 && k.m >= kDataShreds && k.m <= 2 * kDataShreds;
   auto run_pass = [&](int pass) -> int {
     // 1-3. the kept shreds of every slice (the Regular pipeline's steps with this shredder's data
@@ -1007,8 +1027,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
       const size_t wps = k.m > kDataShreds ? 2 : 1;
       const uint64_t* words = v.d_present;
       if (kind != AG_SHREDDER_AONT) {
-        uint8_t* dw;
-        if ((st = pipe_buf(c, kBufCoderWords, 8 * wps * n, &dw)) || (st = c->h_strip.ensure(8 * wps * n))) return st;
+        if ((st = c->h_strip.ensure(8 * wps * n))) return st;
         uint64_t* hw = c->h_strip.as<uint64_t>();
         for (size_t s = 0; s < n; ++s) {
           const uint64_t o = h_present[s];
@@ -1020,8 +1039,8 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
             hw[2 * s + 1] = o >> 63;
           }
         }
-        AG_HIP(hipMemcpyAsync(dw, hw, 8 * wps * n, hipMemcpyHostToDevice, c->stream));
-        words = reinterpret_cast<const uint64_t*>(dw);
+        AG_HIP(hipMemcpyAsync(v.coder_words, hw, 8 * wps * n, hipMemcpyHostToDevice, c->stream));
+        words = v.coder_words;
       }
       // (pipe_coder_deshred reads its results back through h_strip after the upload completed)
       if ((st = pipe_coder_deshred(c, n, S, codewords, cw_stride, words, plen.data(), k.m, !surplus && !full_data)))
@@ -1063,10 +1082,8 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
     // 5. check_merkle_tree over the raw output shreds (before any decryption: they are the
     //    codeword rows)
     if ((st = kind_merkle(c, k, n, S, codewords, cw_stride, v.roots2, v.cols.proof))) return st;
-    uint8_t* same;
-    if ((st = pipe_buf(c, kBufSame, n, &same))) return st;
-    if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
-    AG_HIP(hipMemcpyAsync(h_same.data(), same, n, hipMemcpyDeviceToHost, c->stream));
+    if (ag::launch_pipe_root_cmp(v.roots2, v.sroot, n, v.same, c->stream) != hipSuccess) return AG_RS_ERR_DEVICE;
+    AG_HIP(hipMemcpyAsync(h_same.data(), v.same, n, hipMemcpyDeviceToHost, c->stream));
     AG_HIP(hipStreamSynchronize(c->stream));
     // the slices the ANY_K decode may have wronged (regular_deshred's step 6b)
     rerun.clear();
@@ -1079,7 +1096,7 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
       // the absent datagrams of the slices that decoded and match their root, serialized from
       // the encrypted rows; then decrypt_payload (BadEncoding for a buffer shorter than the key)
       for (size_t s = 0; s < n; ++s) pre_ok[s] = plen[s] >= 0 && h_same[s];
-      if ((st = fill_missing(c, k, n, S, v, pre_ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+      if ((st = fill_missing(c, k, n, S, v, pre_ok.data(), packets, packet_stride))) return st;
       AG_HIP(hipStreamSynchronize(c->stream));
       std::vector<uint32_t> cl(n);
       for (size_t s = 0; s < n; ++s) cl[s] = pre_ok[s] ? static_cast<uint32_t>(plen[s]) : 0;
@@ -1150,11 +1167,11 @@ int ag_shredder_deshred_batch_kind(ag_rs_ctx* c, int kind, size_t nslices, size_
   // 7. fill_missing_shreds: every absent slot of a successful slice gets its datagram (PETS /
   //    AONT serialized theirs from the encrypted rows, before the decrypt)
   if (k.aon < 0) {
-    if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride, &d_ok, &fresh))) return st;
+    if ((st = fill_missing(c, k, n, S, v, ok.data(), packets, packet_stride))) return st;
     AG_HIP(hipStreamSynchronize(c->stream));
   }
-  AG_HIP(hipMemcpyAsync(d_ok, ok.data(), n, hipMemcpyHostToDevice, c->stream));
-  if (ag::launch_pipe_merge_lens(fresh, v.d_present, d_ok, n, packet_lens, c->stream) != hipSuccess)
+  AG_HIP(hipMemcpyAsync(v.slice_ok, ok.data(), n, hipMemcpyHostToDevice, c->stream));
+  if (ag::launch_pipe_merge_lens(v.fresh_lens, v.d_present, v.slice_ok, n, packet_lens, c->stream) != hipSuccess)
     return AG_RS_ERR_DEVICE;
   AG_HIP(hipStreamSynchronize(c->stream));
   return AG_RS_OK;

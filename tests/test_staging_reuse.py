@@ -12,6 +12,12 @@ The composed shred signs on the context's side stream with scratch it shares wit
 validation of the main stream (SideScope in csrc/rs_ctx.hpp): on a fresh context, whose buffers
 start empty, it runs as the first call and again at once with more slices, and directly behind an
 asynchronous validation whose scratch it has to regrow, against shredder_oracle's datagrams.
+
+The composed shredders carve each call's scratch out of one grow-only buffer of the context, grown
+at entry, and the EXACT re-run's out of a second one, grown in mid-call (csrc/shredder_api.cpp).
+On fresh contexts: a shred that keeps roots and signatures in that scratch, regrown at once by a
+larger one; a deshred (Regular, PETS) whose larger layout regrows it under a queued shred; and a
+re-run on a context's first call, then one with more listed slices.
 """
 
 import random
@@ -23,6 +29,7 @@ import merkle_oracle as mk
 import rs_oracle as o
 import shredder_cases as cases
 import shredder_oracle as so
+import test_shredder_exact_rerun as xr
 from alpenglow_amd import rs
 
 N1, N2 = 2, 70           # the second batch is larger: its staging has to grow
@@ -264,7 +271,8 @@ class ShredCall:
     call of a test starts, since an upload from pageable memory waits for the stream), the call
     itself without anything synchronised, and the comparison with the oracle."""
 
-    def __init__(self, dev, slices):
+    def __init__(self, dev, slices, outputs=True):
+        """outputs False: no roots_out / sigs_out, the call keeps both in its own scratch."""
         self.slices = slices
         n = len(slices)
         self.maxd = max(len(s[1]) for s in slices)
@@ -278,8 +286,8 @@ class ShredCall:
         self.cw = torch.full((n, 64 * S_UNI), FILL, dtype=torch.uint8, device=dev)
         self.pkts = torch.full((n * 64, cases.PKT), FILL, dtype=torch.uint8, device=dev)
         self.lens = torch.zeros(n * 64, dtype=torch.int32, device=dev)
-        self.roots = torch.full((n, 32), FILL, dtype=torch.uint8, device=dev)
-        self.sigs = torch.full((n, 64), FILL, dtype=torch.uint8, device=dev)
+        self.roots = torch.full((n, 32), FILL, dtype=torch.uint8, device=dev) if outputs else None
+        self.sigs = torch.full((n, 64), FILL, dtype=torch.uint8, device=dev) if outputs else None
 
     def run(self, c):
         s = self.slices
@@ -288,11 +296,13 @@ class ShredCall:
                                 self.lens, roots_out=self.roots, sigs_out=self.sigs)
 
     def check(self, want):
-        """Packets, packet lengths, roots and signatures against the oracle's; FILL past each datagram."""
-        pkts, lens, roots, sigs = (t.cpu().numpy() for t in (self.pkts, self.lens, self.roots, self.sigs))
+        """Packets, packet lengths, roots and signatures against the oracle's; FILL past each datagram.
+        (Every datagram carries its slice's signature over the root, whoever holds the two.)"""
+        pkts, lens = self.pkts.cpu().numpy(), self.lens.cpu().numpy()
         for b, (datagrams, _, root, sig) in enumerate(want):
-            assert roots[b].tobytes() == root, (len(want), b)
-            assert sigs[b].tobytes() == sig, (len(want), b)
+            if self.roots is not None:
+                assert self.roots[b].cpu().numpy().tobytes() == root, (len(want), b)
+                assert self.sigs[b].cpu().numpy().tobytes() == sig, (len(want), b)
             for j in range(64):
                 t = 64 * b + j
                 assert lens[t] == len(datagrams[j]) == cases.wire_len(S_UNI), (len(want), b, j)
@@ -344,5 +354,165 @@ def test_shredder_shred_batch_behind_a_validation(ctx, dev, shredded):
         c.synchronize()
         assert status.cpu().numpy().tolist() == [rs.SHRED_OK] * 64
         call.check(want[N1:])
+    finally:
+        c.close()
+
+
+# ---- the composed shredders' carved scratch on a fresh context -----------------------------------
+
+@pytest.mark.gpu
+def test_shredder_shred_batch_scratch_roots_regrown(ctx, dev, shredded):
+    """No roots_out / sigs_out: the roots and signatures of 2 slices lie in the call's scratch,
+    which the call of 70 slices behind it regrows while the first one's serialize, side-stream
+    sign and signature patch may still be queued."""
+    slices, want = shredded
+    calls = [ShredCall(dev, slices[:N1], outputs=False), ShredCall(dev, slices[N1:], outputs=False)]
+    c = fresh_context(ctx)
+    try:
+        c.synchronize()
+        for call in calls:  # back to back
+            call.run(c)
+        c.synchronize()
+        calls[0].check(want[:N1])
+        calls[1].check(want[N1:])
+    finally:
+        c.close()
+
+
+class KindShredCall:
+    """ShredCall for rs.shredder_shred_batch_kind, checked with shredder_cases.check_shred."""
+
+    def __init__(self, dev, kind, slices):
+        self.kind, self.slices, self.stride = kind, slices, cases.stride_of(kind, S_UNI)
+        n = len(slices)
+        self.maxd = max(len(s[1]) for s in slices)
+        data = np.zeros((n, self.maxd), np.uint8)
+        for b, s in enumerate(slices):
+            data[b, :len(s[1])] = np.frombuffer(s[1], np.uint8)
+        self.data = to_dev(data, dev)
+        self.slots, self.sidx = (to_dev(np.array([s[i] for s in slices], np.uint64), dev) for i in (2, 3))
+        self.last = to_dev(np.array([s[4] for s in slices], np.uint8), dev)
+        self.seed, self.pk = (to_dev(np.frombuffer(x, np.uint8), dev) for x in (cases.SEED, cases.PK))
+        self.keys = to_dev(np.frombuffer(b"".join(s[5] for s in slices), np.uint8), dev)
+        self.cw = torch.full((n, self.stride), FILL, dtype=torch.uint8, device=dev)
+        self.pkts = torch.full((n * 64, cases.PKT), FILL, dtype=torch.uint8, device=dev)
+        self.lens = torch.zeros(n * 64, dtype=torch.int32, device=dev)
+        self.roots = torch.full((n, 32), FILL, dtype=torch.uint8, device=dev)
+        self.sigs = torch.full((n, 64), FILL, dtype=torch.uint8, device=dev)
+
+    def run(self, c):
+        s = self.slices
+        rs.shredder_shred_batch_kind(c, self.kind, len(s), S_UNI, [x[0] for x in s], self.data, self.maxd,
+                                     [len(x[1]) for x in s], self.slots, self.sidx, self.last, self.seed, self.pk,
+                                     self.keys if cases.extra_of(self.kind) else None, self.cw, self.stride,
+                                     self.pkts, cases.PKT, self.lens, roots_out=self.roots, sigs_out=self.sigs)
+
+    def check(self, want):
+        got = cases.Shredded(*(t.cpu().numpy() for t in (self.cw, self.pkts, self.lens, self.roots, self.sigs)))
+        got.error = None
+        cases.check_shred(got, self.kind, self.slices, S_UNI, want)
+
+
+class DeshredCall:
+    """One rs.shredder_deshred_batch_kind (Regular: ag_shredder_deshred_batch) over datagram slots
+    staged on the device beforehand, checked with shredder_cases.check_deshred."""
+
+    def __init__(self, dev, kind, rows):
+        self.kind, self.rows, self.stride = kind, rows, cases.stride_of(kind, S_UNI)
+        buf, ln = cases.pack(rows)
+        self.buf, self.ln = to_dev(buf, dev), to_dev(ln, dev)
+        self.pk = to_dev(np.frombuffer(cases.PK, np.uint8), dev)
+        self.cw = torch.full((len(rows), self.stride), FILL, dtype=torch.uint8, device=dev)
+
+    def run(self, c):
+        self.res = rs.shredder_deshred_batch_kind(c, self.kind, len(self.rows), S_UNI, self.buf, cases.PKT, self.ln,
+                                                  self.pk, self.cw, self.stride)
+        self.rerun = rs.last_exact_rerun(c)
+
+    def check(self, want):
+        g = cases.Deshredded()
+        g.res, g.buf, g.ln, g.cw = self.res, self.buf.cpu().numpy(), self.ln.cpu().numpy(), self.cw.cpu().numpy()
+        cases.check_deshred(g, self.kind, self.rows, S_UNI, want)
+        return g
+
+
+def arrivals(leader, seed):
+    """Per slice the leader's datagrams that arrived: 32, 40, 64, 31, 33, 48 of them in turn."""
+    rng = random.Random(seed)
+    keeps = [set(rng.sample(range(64), (32, 40, 64, 31, 33, 48)[b % 6])) for b in range(len(leader))]
+    return [[pkts[j] if j in keep else None for j in range(64)] for pkts, keep in zip(leader, keeps)]
+
+
+def honest_expect(slice_, full, row):
+    """shredder_cases.expect's tuple for an honest leader's slice without the oracle's decode: the
+    slice comes back as it was shredded, every slot holds the leader's datagram."""
+    kept = [x is not None for x in row]
+    if sum(kept) < 32:
+        return so.NOT_ENOUGH_SHARDS, None, [x if x is not None else b"" for x in row], kept
+    return so.OK, dict(header=(slice_[2], slice_[3], slice_[4]), parent=slice_[0], data=slice_[1]), list(full), kept
+
+
+def shred_then_deshred(ctx, shred, deshred, shred_want, deshred_want):
+    """On a fresh context: the shred of 2 slices, and at once -- nothing synchronised -- the
+    deshred of 70, whose layout is the larger one: the scratch regrows under the queued serialize,
+    side-stream sign and signature patch."""
+    c = fresh_context(ctx)
+    try:
+        c.synchronize()
+        shred.run(c)
+        deshred.run(c)
+        c.synchronize()
+        shred.check(shred_want)
+        deshred.check(deshred_want)
+        assert deshred.rerun == (0, 0)
+        assert [w[0] for w in deshred_want].count(so.OK) == len(deshred_want) - len(deshred_want[3::6])
+    finally:
+        c.close()
+
+
+@pytest.mark.gpu
+def test_shredder_deshred_batch_behind_a_shred(ctx, dev, shredded):
+    slices, want = shredded
+    rows = arrivals([w[0] for w in want[N1:]], 52)
+    shred_then_deshred(ctx, ShredCall(dev, slices[:N1]), DeshredCall(dev, so.REGULAR, rows), want[:N1],
+                       [cases.expect(r, S_UNI, so.REGULAR) for r in rows])
+
+
+@pytest.mark.gpu
+def test_shredder_deshred_batch_kind_behind_a_shred(ctx, dev):
+    """PETS: the row skip, and two present words per slice in the deshred's scratch.  The oracle's
+    AES is Python, so it shreds the 2 slices and deshreds the first six arrivals (one of each
+    count); the other 64 slices are the device's own shred call's (which
+    test_shredder_pipeline.py pins to the oracle at this size), expected back as they were shredded."""
+    kind = so.PETS
+    slices = cases.random_slices(random.Random(43), kind, S_UNI, N1 + N2)
+    shred_want = [so.shred_kind(kind, *s[:5], cases.SEED, s[5]) for s in slices[:N1]]
+    leader = cases.gpu_leader(ctx, dev, kind, slices[N1:], S_UNI)
+    rows = arrivals([pkts for pkts, _ in leader], 53)
+    want = [cases.expect(r, S_UNI, kind) for r in rows[:6]]
+    want += [honest_expect(s, pkts, r) for s, (pkts, _), r in zip(slices[N1 + 6:], leader[6:], rows[6:])]
+    shred_then_deshred(ctx, KindShredCall(dev, kind, slices[:N1]), DeshredCall(dev, kind, rows), shred_want, want)
+
+
+@pytest.mark.gpu
+def test_shredder_deshred_batch_exact_rerun_first_call_then_regrown(ctx, dev):
+    """A context's first call lists slices for the EXACT re-run (3 slices, 2 of them from a leader
+    that signed a non-codeword, received with surplus shreds: test_shredder_exact_rerun.py's
+    generator); the second lists 6 of 8, so the re-run's scratch regrows in mid-call, behind the
+    call's own queued stages, whose scratch must stay where it is."""
+    batches = [xr.Batch(0x57A6E, 3, [S_UNI] * 3, {1: xr.H32}), xr.Batch(0x57A6F, 8, [S_UNI] * 8, {3: xr.HS, 5: xr.H32})]
+    assert [len(bt.rerun) for bt in batches] == [2, 6]
+    calls = [DeshredCall(dev, so.REGULAR, bt.rows) for bt in batches]
+    c = fresh_context(ctx)
+    try:
+        for bt, call in zip(batches, calls):
+            call.run(c)
+            assert call.rerun == (len(bt.rerun), 1)
+        for bt, call in zip(batches, calls):
+            want = [cases.expect(r, S_UNI, so.REGULAR) for r in bt.rows]
+            assert all(want[b][0] in (so.BAD_ENCODING, so.INVALID_MERKLE_TREE) for b in bt.rerun)
+            g = call.check(want)
+            for b in bt.rerun:  # the codeword rows the scatter wrote back
+                xr._check_failed_rows(g.cw[b], bt.rows[b], S_UNI, b)
     finally:
         c.close()
